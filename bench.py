@@ -7,13 +7,22 @@ building, on-device label-tuple de-duplication), every kernel of the forward -- 
 (queries are sharded by rank).  Prints ONE JSON line on rank 0.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--model zk|lds|lxmert|ensemble] [--precision 1|2|3|4]
-                  [--workload bench|bench-strong|testB|valid] [--dense] [--all-boxes] [--no-cpu] [--no-secondary]
+                  [--workload bench|bench-strong|testB|valid] [--dense] [--all-boxes] [--dump-outputs DIR]
+                  [--full [--no-cpu] [--no-secondary]]
+
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, and the roofline read from the
+same timed steps).  --full adds everything that takes runs of its own: the `cpu_baseline` (CPU port of the same forward, also a
+check of the HIP logits), the `secondary` lines (H2D-inclusive and TSV-fed rates, precision 3, lds, lxmert, padded layout, box
+sweep, shard rates, call latency) and, with --gpus N > 1, the `strong` accounting.  --no-cpu / --no-secondary drop parts of --full.
+--dump-outputs DIR: after the timed steps, what the last step returned, as DIR/<name>.npy (float32): `scores` (the step's per-pair
+score, gathered over the ranks when N > 1) and, for one model at N = 1, that call's `logits` and `probs` (pairs x 2).  Inputs and
+weights are seeded, so two builds run with the same arguments can be compared output for output.
 
 --gpus N > 1 without WORLD_SIZE in the environment: this process spawns the N ranks itself (one process per GPU, RCCL);
 under torchrun / torch.distributed.run it uses the ranks it is given (and refuses a --gpus that contradicts WORLD_SIZE).
 --workload bench-strong: the metric's own job -- ONE 1000-query x 30-candidate set -- cut into N contiguous query blocks (3750 pairs
-per rank at N = 8: "candidate sets shard by query across the 8 GPUs").  With --gpus N > 1 the default (weak) run ALSO times this
-job and reports it as `strong` in the same JSON line, so one invocation shows both accountings.
+per rank at N = 8: "candidate sets shard by query across the 8 GPUs").  With --gpus N > 1 --full the default (weak) run ALSO times
+this job and reports it as `strong` in the same JSON line, so one invocation shows both accountings.
 --workload testB | valid: the reference's file shapes -- 994 queries x 8..30 candidates (testB) / 496 x 9..30 (valid; zk then gets
 the ground-truth label fed to its AM-softmax head, load_data_v4.py:259-263) = ONE job cut into contiguous query blocks (ragged
 shards, strong scaling; run_pretraining_predict_score.py:566, prediction_result/*.txt).
@@ -269,6 +278,26 @@ def run_timed(step, steps, warmup, world, dev, handles):
     return dt, med, gms, gn, gfl, fused + [cls, side_fl]
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(path, last, world):
+    """--dump-outputs: the arrays the last timed step returned, as float32 DIR/<name>.npy.  Past DUMP_BYTES in all, every array keeps
+    the same seeded sample of pair rows (their indices in sample_rows.npy)."""
+    torch.cuda.synchronize()
+    arrs = {k: v.detach().float().cpu().numpy() for k, v in last.items() if world == 1 or k == "scores"}
+    n = len(arrs["scores"])
+    total = sum(x.nbytes for x in arrs.values())
+    if total > DUMP_BYTES:
+        keep = int(DUMP_BYTES // (total // n + 8))
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrs = {k: x[rows] for k, x in arrs.items()}
+        arrs["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, x in arrs.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(x))
+
+
 def spawn_ranks(n, argv):
     """`python bench.py --gpus N` without a launcher: one child per GPU with the torchrun environment contract."""
     s = socket.socket()
@@ -375,9 +404,11 @@ def main():
     ap.add_argument("--queries", type=int, default=1000)
     ap.add_argument("--cands", type=int, default=30)
     ap.add_argument("--chunk", type=int, default=0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own: cpu_baseline, the secondary lines and (N > 1) the strong-scaling job")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline")
     ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of host CPU work spent on the cpu_baseline sample (default 20; the contract test uses less)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary lines (precision 3 on fp32 weights, lds, lxmert, H2D-inclusive)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary lines (precision 3 on fp32 weights, lds, lxmert, H2D-inclusive)")
     ap.add_argument("--fp32-weights", action="store_true", help="seeded weights NOT rounded to bf16 (what a real checkpoint looks like)")
     ap.add_argument("--fuse-attn", type=int, default=-1, help="mms_config.fuse_attention (default: the LIBRARY default, scorers.make_scorer's \"auto\": 2 in precision mode 2, 1 in mode 3): QKV projection + attention in one kernel; 1 = exact-fp32 attention MFMAs (bit-identical to the two-kernel route), 2 = split-bf16 MFMAs")
     ap.add_argument("--box-mu", type=float, default=1.1, help="location of the lognormal box count of the synthetic pairs (1.1 = the documented workload, mean 3.5 boxes)")
@@ -387,6 +418,8 @@ def main():
     ap.add_argument("--all-boxes", action="store_true", help="worst case: every pair has 10 boxes")
     a = ap.parse_args()
     a.fuse_attn_arg = a.fuse_attn
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if a.batch_sweep:
         torch.cuda.set_device(0)
@@ -480,22 +513,28 @@ def main():
             if a.model == "ensemble":
                 merged, _ = scorer.score_prepared(prep, members=False)
                 return merged
-            _, probs = scorer.score_prepared(prep)
-            return probs[:, 1].contiguous()
+            last["logits"], last["probs"] = scorer.score_prepared(prep)
+            return last["probs"][:, 1].contiguous()
 
         def step(first=False):
             sc = score()
             if use_pg:
                 sc = sc.to(gather_dev)
-                return sharding.gather_scores(sc, qid if first else None, pid if first else None, counts=counts_, force_collective=True)
-            return sc, None, None
+                out = sharding.gather_scores(sc, qid if first else None, pid if first else None, counts=counts_, force_collective=True)
+            else:
+                out = sc, None, None
+            last["scores"] = out[0]
+            return out
         return step, feats_, feed_
 
+    last = {}               # what the most recent step returned (--dump-outputs)
     step, feats, feed = make_step(ps, counts, valid=a.workload == "valid")
     dt, med, gemm_ms, gemm_n, gemm_fl, fused = run_timed(step, a.steps, a.warmup, world, dev, handles)
     value = total_pairs * a.steps / dt
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last, world)
     strong = None
-    if world > 1 and a.workload == "bench":
+    if world > 1 and a.workload == "bench" and a.full:
         # the same invocation, strong-scaling accounting: the metric's own 1000-query x 30-candidate job cut over the N ranks
         # (every rank takes part, so this runs on all ranks; rank 0 reports it)
         ps_s, counts_s, total_s, wl_s = one_job("bench-strong")
@@ -601,13 +640,13 @@ def main():
                                   "distinct_devices": len({(d["host"], d["pci_bus_id"], d["uuid"]) for d in rank_devices}),
                                   "shared_device_test_mode": bool(os.environ.get("MMS_BENCH_SHARE_GPU")),
                                   "gather": "one all_gather_into_tensor of fp32 scores per step on %s tensors" % ("device" if backend == "nccl" else "host")}
-        if world == 1 and not a.no_secondary and a.workload == "bench":
+        if a.full and world == 1 and not a.no_secondary and a.workload == "bench":
             res["secondary"] = secondary(a, local, dev, ps, feats, members, scorer, feed, value)
             if "precision3" in res["secondary"]:
                 # the real-checkpoint mode as a top-level value of the line: the same batch scored by a zk handle whose
                 # weights are NOT bf16-rounded (precision "auto" -> mode 3), with its parity against the oracle's fp32 port on the timed batch
                 res["value_fp32_checkpoint"] = res["secondary"]["precision3"]
-        if world == 1 and not a.no_cpu:
+        if a.full and world == 1 and not a.no_cpu:
             n0 = "zk" if a.model == "ensemble" else a.model
             cfg0, w0, s0 = members[n0]
 

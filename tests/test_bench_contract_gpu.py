@@ -11,7 +11,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_bench_prints_one_contract_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--queries", "40", "--cpu-budget", "4"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--queries", "40", "--cpu-budget", "4",
+                          "--full"],
                          cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
@@ -67,3 +68,35 @@ def test_bench_ensemble_and_fp8_lines():
         d = json.loads([l for l in out.stdout.splitlines() if l.strip()][-1])
         assert d["value"] > 0 and d["roofline"]["achieved"] > 0
         assert ("ensemble" in d["config"]["workload"]) == (extra[0] == "--model")
+
+
+@pytest.mark.gpu
+def test_plain_bench_is_lean_and_dumps_its_last_step(tmp_path):
+    """A plain run prints the headline line without the --full measurements; --dump-outputs writes what the last timed step
+    returned (float32), and the seeded inputs make two runs agree array for array."""
+    import numpy as np
+    runs = []
+    for i in range(2):
+        dump = tmp_path / str(i)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--queries", "40",
+                              "--dump-outputs", str(dump)], cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines = [l for l in out.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline"):
+            assert k in d, k
+        assert d["steps"] == 3 and d["unit"] == "pairs/s" and d["higher_is_better"] is True
+        assert abs(d["value"] - 40 * 30 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-3
+        assert "cpu_baseline" not in d and "secondary" not in d and "strong" not in d
+        arr = {k: np.load(dump / (k + ".npy")) for k in ("scores", "logits", "probs")}
+        assert sorted(os.listdir(dump)) == ["logits.npy", "probs.npy", "scores.npy"]
+        assert all(x.dtype == np.float32 and np.isfinite(x).all() for x in arr.values())
+        assert arr["scores"].shape == (1200,) and arr["logits"].shape == arr["probs"].shape == (1200, 2)
+        assert np.array_equal(arr["scores"], arr["probs"][:, 1])
+        lg = arr["logits"].astype(np.float64)
+        sm = np.exp(lg - lg.max(1, keepdims=True))
+        assert np.abs(sm / sm.sum(1, keepdims=True) - arr["probs"]).max() < 1e-5
+        runs.append(arr)
+    for k in runs[0]:
+        assert np.abs(runs[0][k] - runs[1][k]).max() <= 1e-5 * max(1.0, np.abs(runs[0][k]).max()), k

@@ -78,7 +78,7 @@ def test_bench_gpus8_reports_weak_and_strong_in_one_line():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env.update(MMS_BENCH_SHARE_GPU="1", MMS_BENCH_BACKEND="gloo")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--queries", "24",
-                          "--cands", "10"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=2400)
+                          "--cands", "10", "--full"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=2400)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, lines

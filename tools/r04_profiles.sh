@@ -7,9 +7,9 @@ O=$R/gpurun_out/$T
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for m in zk lds lxmert; do
-  python $R/bench.py --model $m --no-secondary $([ $m = zk ] || echo --no-cpu) > $O/bench_$m.json 2> $O/bench_$m.err
+  python $R/bench.py --model $m --full --no-secondary $([ $m = zk ] || echo --no-cpu) > $O/bench_$m.json 2> $O/bench_$m.err
 done
-python $R/bench.py > $O/bench_default.json 2> $O/bench_default.err
+python $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python $R/bench.py --model ensemble --no-cpu --no-secondary > $O/bench_ensemble.json 2> $O/bench_ensemble.err
 python $R/bench.py --precision 4 --no-cpu --no-secondary > $O/bench_zk_fp8.json 2> $O/bench_zk_fp8.err
 python $R/bench.py --model ensemble --precision 4 --no-cpu --no-secondary > $O/bench_ensemble_fp8.json 2> $O/bench_ensemble_fp8.err
@@ -20,7 +20,7 @@ for f in 0 1; do   # mms_config.fuse_attention off / exact-fp32 attention (the l
   python $R/bench.py --fuse-attn $f --no-cpu --no-secondary > $O/bench_zk_fuseattn$f.json 2> $O/bench_zk_fuseattn$f.err
 done
 python $R/bench.py --precision 3 --fp32-weights --no-cpu --no-secondary > $O/bench_zk_mode3.json 2> $O/bench_zk_mode3.err
-MMS_BENCH_SHARE_GPU=1 MMS_BENCH_BACKEND=gloo python $R/bench.py --gpus 2 --no-cpu > $O/bench_zk_2ranks_shared_gpu.json 2> $O/bench_zk_2ranks_shared_gpu.err
+MMS_BENCH_SHARE_GPU=1 MMS_BENCH_BACKEND=gloo python $R/bench.py --gpus 2 --full --no-cpu > $O/bench_zk_2ranks_shared_gpu.json 2> $O/bench_zk_2ranks_shared_gpu.err
 python $R/bench.py --workload testB --no-cpu --no-secondary > $O/bench_zk_testB.json 2> $O/bench_zk_testB.err
 for m in zk ensemble; do
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$m -o $m -- python $R/bench.py --model $m --steps 3 --warmup 1 --no-cpu --no-secondary > $O/prof_$m.log 2>&1

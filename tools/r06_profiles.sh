@@ -8,9 +8,9 @@ O=$R/gpurun_out/$T
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for m in zk lds lxmert; do
-  python $R/bench.py --model $m --no-secondary $([ $m = zk ] || echo --no-cpu) > $O/bench_$m.json 2> $O/bench_$m.err
+  python $R/bench.py --model $m --full --no-secondary $([ $m = zk ] || echo --no-cpu) > $O/bench_$m.json 2> $O/bench_$m.err
 done
-( time python $R/bench.py > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_wall.txt
+( time python $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_wall.txt
 python $R/bench.py --model ensemble --no-cpu --no-secondary > $O/bench_ensemble.json 2> $O/bench_ensemble.err
 python $R/bench.py --precision 4 --no-cpu --no-secondary > $O/bench_zk_fp8.json 2> $O/bench_zk_fp8.err
 python $R/bench.py --model ensemble --precision 4 --no-cpu --no-secondary > $O/bench_ensemble_fp8.json 2> $O/bench_ensemble_fp8.err
@@ -22,7 +22,7 @@ for m in zk lxmert lds; do for f in 0 1; do   # same-box A/B of mms_config.fuse_
 done; done
 python $R/bench.py --precision 3 --fp32-weights --no-cpu --no-secondary > $O/bench_zk_mode3.json 2> $O/bench_zk_mode3.err
 python $R/bench.py --precision 3 --fp32-weights --fuse-attn 2 --no-cpu --no-secondary > $O/bench_zk_mode3_fuseattn2.json 2> $O/bench_zk_mode3_fuseattn2.err
-MMS_BENCH_SHARE_GPU=1 MMS_BENCH_BACKEND=gloo python $R/bench.py --gpus 2 --no-cpu > $O/bench_zk_2ranks_shared_gpu.json 2> $O/bench_zk_2ranks_shared_gpu.err
+MMS_BENCH_SHARE_GPU=1 MMS_BENCH_BACKEND=gloo python $R/bench.py --gpus 2 --full --no-cpu > $O/bench_zk_2ranks_shared_gpu.json 2> $O/bench_zk_2ranks_shared_gpu.err
 for m in zk lxmert ensemble; do
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$m -o $m -- python $R/bench.py --model $m --steps 3 --warmup 1 --no-cpu --no-secondary > $O/prof_$m.log 2>&1
   find $O/prof_$m -name "*kernel_stats.csv" -exec cp {} $O/bench_${m}_kernel_stats.csv \;
