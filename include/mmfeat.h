@@ -60,6 +60,9 @@ typedef struct mmf_batch_out {
     int32_t* feat_rows_live;    /* [B] or NULL.  In: how many leading box rows of feats[i] may be non-zero (a fresh buffer: 10); out: the
                                  * record's box count.  With it the zero padding of a REUSED buffer is written only where the row's
                                  * previous record left data (60 % of the bytes of a row at 3.8 boxes per record); NULL: always. */
+    int64_t* feat_span;         /* [B,2] or NULL: byte range of the features field (the 6th) inside `data`, like query_span -- with feats == NULL,
+                                 * what a caller that decodes the features on the GPU gathers (mmf_gather_spans, then mms_decode_feats_b64 of
+                                 * include/mmscore.h).  The field's base64 length is checked against num_boxes either way. */
 } mmf_batch_out;
 
 /* lines: `n` records in one buffer, record i = data[offsets[i] .. offsets[i+1]) (no trailing newline needed).
@@ -72,6 +75,14 @@ int mmf_featurize(const mmf_context* c, const char* data, const int64_t* offsets
 /* Same, with record i = data[starts[i] .. ends[i]) -- records need not be contiguous (skipped header / blank lines). */
 int mmf_featurize_spans(const mmf_context* c, const char* data, const int64_t* starts, const int64_t* ends, int64_t n,
                         int32_t text_len, int32_t box_dim, int32_t sen2forest, int32_t threads, const mmf_batch_out* out);
+
+/* Copy n byte spans data[src[k] .. src[k] + len[k]) to dst + dst_off[k] on `threads` threads of the context's pool (<= 0: the default).
+ * The device feature decode's feed: src = feat_span[k][0], len = ceil(min(num_boxes, 10) x 8192 x 4 / 3) (the characters the decoder reads; the field holds
+ * at least that many once mmf_featurize* has checked its length), dst_off = exclusive prefix sum of the lengths rounded up to 16, and dst sized to
+ * dst_off[n-1] + the last length rounded up to 16 (mms_decode_feats_b64's padding rule).  The bytes between spans are not written.  Calls on one context
+ * run one at a time (mmf_featurize* included).  Returns 0, or -1 on a bad argument (negative offset / length, NULL pointer with n > 0). */
+int mmf_gather_spans(const mmf_context* c, const char* data, const int64_t* src, const int64_t* len, int64_t n, char* dst,
+                     const int64_t* dst_off, int32_t threads);
 
 /* Line splitter for a raw TSV buffer: fills starts/ends (newline excluded) for up to max_lines records, skipping blank
  * lines and lines containing "product_id" (the header test of code/lxmert/src/tasks/kdd_data.py:70-71).  *consumed = bytes of

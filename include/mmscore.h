@@ -172,11 +172,11 @@ typedef struct mms_ensemble_batch {
 /* ABI revision of the structs and entry points declared in this header.  It changes whenever a struct gains a field or an entry
  * point changes its signature (r1: 1; r2 added mms_config.fuse_layernorm, mms_zk_batch.label_ids, mms_lxmert_batch.label_ids / x_norm
  * without bumping it; r3: 3, then 4 with mms_config.fuse_attention; r4: 5 -- mms_dbg_gemm takes the engine per call,
- * the process-global mms_set_gemm_variant and the lab engines' hooks left the product library, fuse_layernorm became a mask; r5: 6 -- mms_dbg_qkv_attn and mms_side_lane_flops added).  A caller built against another revision would make the library read past its structs, so compare
+ * the process-global mms_set_gemm_variant and the lab engines' hooks left the product library, fuse_layernorm became a mask; r5: 6 -- mms_dbg_qkv_attn and mms_side_lane_flops added; r7: 7 -- mms_decode_feats_b64 added).  A caller built against another revision would make the library read past its structs, so compare
  * BEFORE the first mms_create:  if (mms_version() != MMS_ABI_VERSION) abort();   (lib.py's load() does) */
-#define MMS_ABI_VERSION 6
+#define MMS_ABI_VERSION 7
 int mms_version(void);
-const char* mms_global_error(void);              /* message of the last failing mms_create */
+const char* mms_global_error(void);              /* message of the last failing mms_create / mms_decode_feats_b64 */
 
 int mms_create(const mms_config* cfg, mms_handle** out);
 void mms_destroy(mms_handle* h);
@@ -236,6 +236,22 @@ int mms_score_lxmert(mms_handle* h, const mms_lxmert_batch* b, float* logits, fl
  * main.py reads from the score files).  The three handles must live on the same device; zk and lds share text_len. */
 int mms_score_ensemble(mms_handle* zk, mms_handle* lds, mms_handle* lxmert, const mms_ensemble_batch* b, const float* weights4,
                        float* merged, float* member_scores, void* stream);
+
+/* Box features of B records from their base64 text (the TSV's 6th field: f32 [num_boxes, 2048] row-major), decoded on the device --
+ * the host gathers the text (libmmfeat mmf_gather_spans) instead of decoding it, and the H2D copy carries ~42 KB per record instead of 80 KB.
+ *   record i's text starts at chars + char_off[i], a multiple of 16 bytes from `chars` (itself 16-byte aligned); rows[i] = min(num_boxes, 10)
+ *   (clamped to [0, 10] here).  The first ceil(rows[i] x 8192 x 4 / 3) characters are read, decoded in loads of 16.
+ *   Padding rule: the last load of record i covers characters char_off[i] .. char_off[i] + round_up(ceil(rows[i] x 8192 x 4 / 3), 16) - 1,
+ *   so the buffer behind `chars` must extend to at least that byte for every record (mmf_gather_spans's dst_off layout: an exclusive prefix
+ *   sum of the lengths rounded up to 16, plus the last record's rounded length).
+ *   feats[i, :rows[i]] = the decoded floats and feats[i, rows[i]:10] = 0: bit for bit what libmmfeat's host decoder writes (NaN payloads included).
+ *   bad[i] = 1 if one of the characters read is outside the base64 alphabet ('=' included) -- where libmmfeat rejects the record -- or if
+ *   char_off[i] is negative or not a multiple of 16 (nothing is read; the row is zeroed); 0 otherwise.  Characters past the count above
+ *   (the rest of the last load, the text of rows past the 10th) are ignored.  A malformed record sets bad[i] and writes nothing outside feats[i].
+ *   chars, char_off, rows, feats [B,10,2048] fp32 and bad [B] int32 are device pointers; one kernel, asynchronous on `stream`.
+ *   Returns MMS_ERR_ARG (message in mms_global_error, nothing launched) for B < 0, a NULL pointer with B > 0, or a misaligned chars / feats;
+ *   B == 0 launches nothing and returns 0.  Handle-free: it needs no model. */
+int mms_decode_feats_b64(const char* chars, const int64_t* char_off, const int32_t* rows, int64_t B, float* feats, int32_t* bad, void* stream);
 
 /* accumulated hipEvent time (ms) and launch count of the GEMM kernels since the last reset;
  * enable = 1 brackets every GEMM launch with events on its stream (bench / roofline only) */

@@ -1754,6 +1754,17 @@ int mms_version(void) { return MMS_ABI_VERSION; }
 const char* mms_global_error(void) { return g_err.c_str(); }
 const char* mms_last_error(const mms_handle* h) { return h ? h->err.c_str() : "null handle"; }
 
+int mms_decode_feats_b64(const char* chars, const int64_t* char_off, const int32_t* rows, int64_t B, float* feats, int32_t* bad, void* stream) {
+    if (B < 0 || B > INT32_MAX) { g_err = "mms_decode_feats_b64: B must be in [0, 2^31)"; return MMS_ERR_ARG; }
+    if (B == 0) return 0;
+    if (!chars || !char_off || !rows || !feats || !bad) { g_err = "mms_decode_feats_b64: null pointer"; return MMS_ERR_ARG; }
+    if ((reinterpret_cast<uintptr_t>(chars) | reinterpret_cast<uintptr_t>(feats)) & 15) { g_err = "mms_decode_feats_b64: chars and feats must be 16-byte aligned"; return MMS_ERR_ARG; }
+    launch_decode_feats_b64(chars, char_off, rows, B, feats, bad, (hipStream_t)stream);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { g_err = std::string("mms_decode_feats_b64: ") + hipGetErrorString(e); return MMS_ERR_HIP; }
+    return 0;
+}
+
 int mms_create(const mms_config* cfg, mms_handle** out) {
     if (!cfg || !out) { g_err = "null argument"; return MMS_ERR_ARG; }
     *out = nullptr;

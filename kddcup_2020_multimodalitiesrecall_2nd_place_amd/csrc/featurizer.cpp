@@ -344,6 +344,7 @@ bool featurize_one(const mmf_context* c, const char* data, const char* line, int
         b64_decoded_size(f[6].p, f[6].n) != n * 8) { msg = "base64 payload size does not match num_boxes"; return false; }
     o->product_id[i] = pid;
     o->query_id[i] = qid;
+    if (o->feat_span) { o->feat_span[2 * i] = f[5].p - data; o->feat_span[2 * i + 1] = f[5].p - data + f[5].n; }
     o->num_boxes[i] = (int32_t)n;
     const int64_t nb = n < N_BOX ? n : N_BOX;
 
@@ -554,6 +555,27 @@ int mmf_release_later(const mmf_context* c, const void* addr, int64_t len) {
         std::lock_guard<std::mutex> g(c->release_m);
         c->release_q.emplace_back((void*)lo, (size_t)(hi - lo));
     }
+    return 0;
+}
+
+int mmf_gather_spans(const mmf_context* c, const char* data, const int64_t* src, const int64_t* len, int64_t n, char* dst,
+                     const int64_t* dst_off, int32_t threads) {
+    if (!c || n < 0 || (n > 0 && (!data || !src || !len || !dst || !dst_off))) { g_err = "mmf_gather_spans: bad argument"; return -1; }
+    for (int64_t k = 0; k < n; ++k)
+        if (len[k] < 0 || src[k] < 0 || dst_off[k] < 0) { g_err = "mmf_gather_spans: span " + std::to_string(k) + " has a negative offset or length"; return -1; }
+    if (n == 0) return 0;
+    int nt = threads > 0 ? threads : default_threads();
+    if (nt < 1) nt = 1;
+    if ((int64_t)nt > n) nt = (int)n;
+    std::atomic<int64_t> next(0);
+    c->pool.run(nt, [&](int) {
+        for (;;) {
+            const int64_t k0 = next.fetch_add(16);            // ~16 x 20 KB per work item, like mmf_featurize_spans's record items
+            if (k0 >= n) break;
+            const int64_t k1 = k0 + 16 < n ? k0 + 16 : n;
+            for (int64_t k = k0; k < k1; ++k) std::memcpy(dst + dst_off[k], data + src[k], (size_t)len[k]);
+        }
+    });
     return 0;
 }
 

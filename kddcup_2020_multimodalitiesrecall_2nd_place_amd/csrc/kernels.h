@@ -268,3 +268,6 @@ void launch_f8_to_f32(const unsigned char* in, float* out, long long n, hipStrea
 // weight rows [N][K] fp32 (N % 64 == 0, K % 128 == 0) -> e4m3 bytes in 8 x 128-byte tiles + one power-of-two scale per row (the smallest
 // 2^e with max|w| / 2^e <= 448) as e8m0 bytes packed for gemm_mx8_kernel (scale4) and, optionally, as fp32 (scale)
 void launch_quant_rows_f8(const float* w, unsigned char* out, float* scale, unsigned* scale4, int N, int K, hipStream_t st);
+
+// featdecode.hip: box features of B records from their gathered base64 text -> feats [B,10,2048] fp32 (mms_decode_feats_b64 checks the arguments)
+void launch_decode_feats_b64(const char* chars, const int64_t* char_off, const int32_t* rows, long long B, float* feats, int32_t* bad, hipStream_t st);

@@ -3,6 +3,8 @@
 Same outputs as ``featurizer.read_line`` + ``featurizer.{zk,lds,lxmert}_batch`` (tests/test_featurizer_native.py),
 written straight into pinned host buffers when torch is available so each array needs one H2D copy.
 Queries with non-ASCII bytes are tokenised by the Python ``WordPieceTokenizer`` (full Unicode rules).
+With ``feat_decode="device"`` the 2048-d box features are not decoded on the host: the batch carries their base64 text, gathered into a
+pinned buffer, and ``decode_features`` turns it into the [B,10,2048] fp32 tensor on the GPU (libmmscore ``mms_decode_feats_b64``).
 """
 from __future__ import annotations
 
@@ -17,12 +19,15 @@ from .config import FEAT_DIM, LABEL_LEN, N_BOX
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libmmfeat.so")
 EXPORTS = ("mmf_create", "mmf_destroy", "mmf_last_error", "mmf_set_label", "mmf_tokenize_ascii", "mmf_featurize",
-           "mmf_featurize_spans", "mmf_split_lines", "mmf_b64_tier", "mmf_prefault", "mmf_release_later", "mmf_query_ids")
+           "mmf_featurize_spans", "mmf_split_lines", "mmf_b64_tier", "mmf_prefault", "mmf_release_later", "mmf_query_ids",
+           "mmf_gather_spans")
+FEAT_TEXT_KEYS = ("feat_chars", "feat_char_off", "feat_rows")      # the batch keys of feat_decode="device" (decode_features reads them)
 
 
 class BatchOut(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("product_id", "query_id", "num_boxes", "boxes", "feats", "label_ids", "label_len",
-                                          "query_ids", "query_len", "needs_host_tokenizer", "query_span", "feat_rows_live")]
+                                          "query_ids", "query_len", "needs_host_tokenizer", "query_span", "feat_rows_live",
+                                          "feat_span")]
 
 
 _lib = None
@@ -53,8 +58,49 @@ def load(path=None):
             l.mmf_prefault.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
             l.mmf_release_later.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
             l.mmf_query_ids.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        if hasattr(l, "mmf_gather_spans"):
+            l.mmf_gather_spans.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32]
         _lib = l
     return _lib
+
+
+def feat_text_layout(num_boxes):
+    """-> (characters read per record, their offsets in the gathered buffer, its size): ceil(min(num_boxes, 10) x 8192 x 4 / 3) characters per
+    record, offsets an exclusive prefix sum of the lengths rounded up to 16, the size the last offset + the last rounded length (at least 16) --
+    mms_decode_feats_b64's layout and padding rule (include/mmscore.h)."""
+    rows = np.clip(np.asarray(num_boxes, np.int64), 0, N_BOX)
+    need = (rows * (FEAT_DIM * 4 * 4) + 2) // 3
+    padded = (need + 15) & ~np.int64(15)
+    off = np.zeros(len(rows), np.int64)
+    if len(rows) > 1:
+        np.cumsum(padded[:-1], out=off[1:])
+    size = int(off[-1] + padded[-1]) if len(rows) else 0
+    return need, off, max(size, 16) if len(rows) else 0
+
+
+def decode_features(batch: dict, device=None):
+    """Box features of a ``feat_decode="device"`` batch whose ``FEAT_TEXT_KEYS`` arrays are already on the GPU: -> (feats [B,10,2048] fp32,
+    bad [B] int32), both device tensors, computed by ONE kernel on the current stream (nothing waits for it).  bad[i] = 1: record i has a
+    character outside the base64 alphabet where the host decoder would have rejected it -- check before using its scores."""
+    import torch
+
+    from . import lib as _lib
+    chars, off, rows = (batch[k] for k in FEAT_TEXT_KEYS)
+    dev = torch.device(device) if device is not None else chars.device
+    for t, dt in ((chars, torch.uint8), (off, torch.int64), (rows, torch.int32)):
+        if not (torch.is_tensor(t) and t.device == dev and t.dtype == dt and t.is_contiguous()):
+            raise ValueError("decode_features: %s must be contiguous %s tensors on %s" % ("/".join(FEAT_TEXT_KEYS), "uint8/int64/int32", dev))
+    B = rows.shape[0]
+    if off.shape[0] != B:
+        raise ValueError("decode_features: %d offsets for %d records" % (off.shape[0], B))
+    feats = torch.empty((B, N_BOX, FEAT_DIM), dtype=torch.float32, device=dev)
+    bad = torch.empty((B,), dtype=torch.int32, device=dev)
+    l = _lib.load()
+    ptr = lambda t: t.data_ptr() if t.numel() else None
+    rc = l.mms_decode_feats_b64(ptr(chars), ptr(off), ptr(rows), B, ptr(feats), ptr(bad), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise _lib.MmsError("mms_decode_feats_b64 failed (%d): %s" % (rc, l.mms_global_error().decode()))
+    return feats, bad
 
 
 def _host(shape, dtype, pinned):
@@ -70,15 +116,23 @@ class NativeFeaturizer:
     """model: 'zk' | 'lds' | 'lxmert' (box_dim, text_len, tokenizer flavour follow the sub-project)."""
 
     def __init__(self, vocab_path: str, label_table: dict, model: str = "zk", threads: int = 0, pinned: bool = False,
-                 reuse_buffers: bool = False, pools: int = 1, want_feats: bool = True):
+                 reuse_buffers: bool = False, pools: int = 1, want_feats: bool = True, feat_decode: str = "host"):
         """reuse_buffers: keep ``pools`` (pinned) sets of output buffers, grown on demand and used round-robin -- the
         returned arrays are then views that the ``pools``-th following call overwrites (streaming use: featurize ->
         H2D copy -> featurize ...).  Page-faulting fresh 336 KB/row buffers costs more than the decode itself, so the
         streaming drivers turn this on.  want_feats=False: the 2048-d box features are neither decoded nor allocated (the batch dicts
-        carry None for them) -- for a second pass over records whose features another featurizer already produced."""
-        self.want_feats = want_feats
+        carry None for them) -- for a second pass over records whose features another featurizer already produced.
+        feat_decode: "host" (default) decodes the features into ``feats``; "device" leaves ``feats`` None and gathers each record's base64
+        text instead -- ``feat_chars`` (pinned uint8, grown and reused like the other buffers), ``feat_char_off`` (int64 [B]) and ``feat_rows``
+        (int32 [B] = min(num_boxes, 10)) -- for ``decode_features`` on the GPU.  Every other array is the host mode's."""
+        if feat_decode not in ("host", "device"):
+            raise ValueError("feat_decode must be 'host' or 'device', not %r" % (feat_decode,))
+        self.want_feats, self.feat_decode = want_feats, feat_decode
+        self.host_feats = want_feats and feat_decode == "host"          # decode into feats
+        self.gather_feats = want_feats and feat_decode == "device"      # gather the text for the device decode
         self.lib = load()
         self.reuse, self._caps, self._pools, self._turn = reuse_buffers, [0] * pools, [None] * pools, 0
+        self._chars, self._last = [None] * pools, 0                     # feat_decode="device": one text buffer per pool
         self.model = model
         self.text_len = 23 if model == "lxmert" else 20
         self.box_dim = 4 if model == "lxmert" else 5
@@ -105,10 +159,11 @@ class NativeFeaturizer:
     def _spec(self, n):
         T = self.text_len
         return dict(product_id=((n,), np.int64), query_id=((n,), np.int64), num_boxes=((n,), np.int32),
-                    boxes=((n, N_BOX, self.box_dim), np.float32), feats=((n if self.want_feats else 0, N_BOX, FEAT_DIM), np.float32),
+                    boxes=((n, N_BOX, self.box_dim), np.float32), feats=((n if self.host_feats else 0, N_BOX, FEAT_DIM), np.float32),
                     label_ids=((n, N_BOX, LABEL_LEN), np.int32), label_len=((n, N_BOX), np.int32),
                     query_ids=((n, T), np.int32), query_len=((n,), np.int32), needs_host_tokenizer=((n,), np.uint8),
-                    query_span=((n, 2), np.int64))
+                    query_span=((n, 2), np.int64),
+                    **(dict(feat_span=((n, 2), np.int64), feat_char_off=((n,), np.int64), feat_rows=((n,), np.int32)) if self.gather_feats else {}))
 
     def _buffers(self, n):
         if not self.reuse:
@@ -116,6 +171,7 @@ class NativeFeaturizer:
             return {k: v[0] for k, v in pairs.items()}, {k: v[1] for k, v in pairs.items()}
         t = self._turn
         self._turn = (t + 1) % len(self._pools)
+        self._last = t
         if n > self._caps[t]:
             self._caps[t] = max(n, 2 * self._caps[t])
             self._pools[t] = {k: _host(shape, dt, self.pinned) for k, (shape, dt) in self._spec(self._caps[t]).items()}
@@ -123,7 +179,7 @@ class NativeFeaturizer:
             # the count per row, and only the part of the zero padding that a previous record wrote over is written again
             live = np.full(self._caps[t], N_BOX, np.int32)
             self._pools[t]["feat_rows_live"] = (live, live)
-        return {k: (v[0][:n] if (k != "feats" or self.want_feats) else v[0]) for k, v in self._pools[t].items()}, {k: v[1] for k, v in self._pools[t].items()}
+        return {k: (v[0][:n] if (k != "feats" or self.host_feats) else v[0]) for k, v in self._pools[t].items()}, {k: v[1] for k, v in self._pools[t].items()}
 
     def featurize(self, lines, sen2forest: bool = False) -> dict:
         """lines: iterable of TSV records (str or bytes).  Returns the raw padded arrays (+ ``keep`` = pinned owners)."""
@@ -144,10 +200,11 @@ class NativeFeaturizer:
         n, T = len(starts), self.text_len
         arr, keep = self._buffers(n)
         live = arr.pop("feat_rows_live", None)                    # reused buffer sets only
-        out = BatchOut(*([(arr[k].ctypes.data if (k != "feats" or self.want_feats) else None)
+        out = BatchOut(*([(arr[k].ctypes.data if (k != "feats" or self.host_feats) else None)
                           for k in ("product_id", "query_id", "num_boxes", "boxes", "feats", "label_ids",
                                     "label_len", "query_ids", "query_len", "needs_host_tokenizer", "query_span")]
-                         + [live.ctypes.data if live is not None and n else None]))
+                         + [live.ctypes.data if live is not None and n else None]
+                         + [arr["feat_span"].ctypes.data if self.gather_feats else None]))
         if n:
             import time
             t0 = time.perf_counter()
@@ -156,6 +213,7 @@ class NativeFeaturizer:
             self.stats["decode"] = self.stats.get("decode", 0.0) + time.perf_counter() - t0
             if rc != 0:
                 raise ValueError("mmf_featurize failed (%d): %s" % (rc, self.lib.mmf_last_error().decode()))
+        chars_owner = self._gather(base, arr) if self.gather_feats else None
         for i in np.nonzero(arr["needs_host_tokenizer"])[0]:      # non-ASCII queries: full Unicode tokenizer
             q = getbytes(int(arr["query_span"][i, 0]), int(arr["query_span"][i, 1])).decode("utf-8")
             if sen2forest:
@@ -165,9 +223,38 @@ class NativeFeaturizer:
             arr["query_ids"][i] = 0
             arr["query_ids"][i, :min(T, len(ids))] = ids[:T]
         arr["keep"] = keep
-        if not self.want_feats:
+        if chars_owner is not None:
+            keep["feat_chars"] = chars_owner
+        if not self.host_feats:
             arr["feats"] = None
         return arr
+
+    def _gather(self, base, arr):
+        """feat_decode="device": the characters of each record's features that the device decoder reads -> one pinned buffer (mmf_gather_spans on the
+        context's threads); fills feat_rows / feat_char_off and sets ``feat_chars`` to the used part of the buffer."""
+        import time
+        n = arr["num_boxes"].shape[0]
+        need, off, size = feat_text_layout(arr["num_boxes"])
+        arr["feat_rows"][:] = np.clip(arr["num_boxes"], 0, N_BOX)
+        arr["feat_char_off"][:] = off
+        if not self.reuse:                                        # fresh buffers per call, like the other arrays
+            buf = _host((size,), np.uint8, self.pinned and size > 0)
+        else:                                                     # one per buffer set, grown geometrically
+            t = self._last
+            if self._chars[t] is None or self._chars[t][0].size < size:
+                cap = max(size, 2 * (self._chars[t][0].size if self._chars[t] is not None else 0))
+                self._chars[t] = _host((cap,), np.uint8, self.pinned and cap > 0)
+            buf = self._chars[t]
+        chars = buf[0]
+        if n:
+            src = np.ascontiguousarray(arr["feat_span"][:, 0])
+            t0 = time.perf_counter()
+            rc = self.lib.mmf_gather_spans(self._h, base, src.ctypes.data, need.ctypes.data, n, chars.ctypes.data, off.ctypes.data, self.threads)
+            self.stats["gather"] = self.stats.get("gather", 0.0) + time.perf_counter() - t0
+            if rc != 0:
+                raise ValueError("mmf_gather_spans failed (%d): %s" % (rc, self.lib.mmf_last_error().decode()))
+        arr["feat_chars"] = chars[:size]
+        return buf[1]
 
     def query_ids(self, path: str) -> np.ndarray:
         """query_id of every record of a TSV file, in file order (int64), without decoding a record: line split + the last field.  A rank of
@@ -309,18 +396,19 @@ class NativeFeaturizer:
 
     def _layout(self, a: dict) -> dict:
         n, T = a["product_id"].shape[0], self.text_len
+        text = {k: a[k] for k in FEAT_TEXT_KEYS if k in a}              # feat_decode="device": the features' base64 text
         if self.model == "zk":
-            return {"num_boxes": a["num_boxes"], "np_boxes_5": a["boxes"], "np_images_features": a["feats"],
+            return {**text, "num_boxes": a["num_boxes"], "np_boxes_5": a["boxes"], "np_images_features": a["feats"],
                     "np_idx_class_labels": a["label_ids"], "np_idx_query_": a["query_ids"], "len_query_": a["query_len"],
                     "labels": np.ones(n, np.int64), "segment_ids": np.tile(np.array([0] * T + [1] * N_BOX, np.int32), (n, 1)),
                     "query_id": a["query_id"], "product_id": a["product_id"]}
         if self.model == "lds":
-            return {"input_ids": a["query_ids"].astype(np.int64), "segment_ids": np.zeros((n, T), np.int64), "boxes": a["boxes"],
+            return {**text, "input_ids": a["query_ids"].astype(np.int64), "segment_ids": np.zeros((n, T), np.int64), "boxes": a["boxes"],
                     "features": a["feats"], "labelfeat": a["label_ids"].astype(np.int64), "next_sentence_labels": np.zeros(n, np.int64),
                     "query_id": a["query_id"], "product_id": a["product_id"]}
         nb = np.minimum(a["num_boxes"], N_BOX)
         lens = np.minimum(a["query_len"], T)
-        return {"input_ids": a["query_ids"].astype(np.int64), "boxes_label_input_ids": a["label_ids"].astype(np.int64),
+        return {**text, "input_ids": a["query_ids"].astype(np.int64), "boxes_label_input_ids": a["label_ids"].astype(np.int64),
                 "input_mask": (np.arange(T)[None, :] < lens[:, None]).astype(np.int64),
                 "boxes_label_input_mask": (np.arange(LABEL_LEN)[None, None, :] < np.minimum(a["label_len"], LABEL_LEN)[:, :, None]).astype(np.int64),
                 "feats": a["feats"], "boxes": a["boxes"],

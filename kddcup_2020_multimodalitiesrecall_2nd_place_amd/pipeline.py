@@ -59,7 +59,8 @@ def kdd_predict(scorer, tsv_lines, label_table, tokenizer, save_path=None, batch
     return match_pred, match_label, rank_score_pred
 
 
-_FEATURIZERS: dict = {}
+_FEATURIZERS: dict = {}                  # key -> NativeFeaturizer, least recently used first
+_FEATURIZER_CACHE = 6
 _COPY_STREAMS: dict = {}
 
 
@@ -73,16 +74,37 @@ def _copy_stream(dev):
     return _COPY_STREAMS[key]
 
 
-def _cached_featurizer(vocab_path, label_table, model, threads, want_feats=True, slot=0):
+def _cached_featurizer(vocab_path, label_table, model, threads, want_feats=True, slot=0, feat_decode="host", protect=()):
     """One NativeFeaturizer (helper threads + three pinned buffer sets, ~2 GB at 8192-record batches) per (vocabulary, label table, model,
-    threads): creating them costs about as much as decoding 30 000 records."""
+    threads, feature decode mode): creating them costs about as much as decoding 30 000 records.  At most ``_FEATURIZER_CACHE`` are kept; a miss
+    closes the least recently used one, never one of ``protect`` (the featurizers a caller has fetched for the same pass)."""
     from .featurizer_native import NativeFeaturizer
-    key = (os.path.abspath(vocab_path), os.path.getmtime(vocab_path), model, threads, want_feats, slot, tuple(sorted((int(k), v) for k, v in label_table.items())))
-    if key not in _FEATURIZERS:
-        if len(_FEATURIZERS) >= 6:
-            _FEATURIZERS.pop(next(iter(_FEATURIZERS))).close()
-        _FEATURIZERS[key] = NativeFeaturizer(vocab_path, label_table, model, threads=threads, pinned=True, reuse_buffers=True, pools=3, want_feats=want_feats)
-    return _FEATURIZERS[key]
+    key = (os.path.abspath(vocab_path), os.path.getmtime(vocab_path), model, threads, want_feats, slot, feat_decode,
+           tuple(sorted((int(k), v) for k, v in label_table.items())))
+    nf = _FEATURIZERS.pop(key, None)
+    if nf is None:
+        victims = [k for k, v in _FEATURIZERS.items() if not any(v is p for p in protect)]
+        while len(_FEATURIZERS) >= _FEATURIZER_CACHE and victims:
+            _FEATURIZERS.pop(victims.pop(0)).close()
+        nf = NativeFeaturizer(vocab_path, label_table, model, threads=threads, pinned=True, reuse_buffers=True, pools=3, want_feats=want_feats,
+                              feat_decode=feat_decode)
+    _FEATURIZERS[key] = nf               # (re)inserted last: the most recently used
+    return nf
+
+
+_FEAT_KEY = {"zk": "np_images_features", "lds": "features", "lxmert": "feats"}     # the features' key in each model's batch layout
+
+
+def _check_decoded(bads, pids):
+    """feat_decode="device": the per-batch ``bad`` flags of the pass (device tensors, one read-back) -> ValueError naming the first bad record."""
+    import torch
+    if not bads:
+        return
+    hit = torch.nonzero(torch.cat(bads)).flatten()
+    if hit.numel():
+        i = int(hit[0])
+        raise ValueError("record %d of the pass (product_id %d): bad base64 in features (decoded on the device; %d bad record(s))"
+                         % (i, int(np.concatenate(pids)[i]), hit.numel()))
 
 
 def tsv_shard(nf, tsv_path, rank: int, world: int):
@@ -112,7 +134,7 @@ def decode_threads_for(world: int) -> int:
 
 
 def stream_scores_tsv(scorer, tsv_path, vocab_path, label_table, sen2forest: bool = False, batch_pairs: int = 32768, threads: int = 0,
-                      ramp: int = 1024, shard=None, shard_by: str = "bytes", stats: dict = None):
+                      ramp: int = 1024, shard=None, shard_by: str = "bytes", stats: dict = None, feat_decode: str = "host"):
     """TSV file -> (query_id, product_id, score) with the three stages overlapped:
 
       producer thread   libmmfeat decodes batch i+2 into one of three pinned buffer sets (ctypes releases the GIL)
@@ -128,16 +150,23 @@ def stream_scores_tsv(scorer, tsv_path, vocab_path, label_table, sen2forest: boo
     boundaries near size * r / world (``NativeFeaturizer.byte_shard``: O(1) per rank, shards balanced by decode work; ``counts`` is None -- the gather
     exchanges the sizes).  ``shard_by="queries"``: equal numbers of queries per rank (``tsv_shard``: every rank indexes the whole file first -- an
     index pass per rank that costs more than the decode from ~4 ranks on, profiles/rd6_feat_sweep.txt -- and gets the static ``counts`` list).
+
+    ``feat_decode="device"``: the featurizer gathers the box features' base64 text instead of decoding it (~42 KB per record over PCIe instead
+    of 80 KB), the copy stream carries it with the other arrays, and ``featurizer_native.decode_features`` runs on the scoring stream in front of
+    the scorer's kernels.  Scores are bit-identical to the host mode's; a record whose text is not base64 raises ValueError (naming it) before
+    the pass returns.
     """
     import queue
     import threading
 
     import torch
 
-    from .featurizer_native import NativeFeaturizer
+    from .featurizer_native import decode_features
+    if feat_decode not in ("host", "device"):
+        raise ValueError("feat_decode must be 'host' or 'device', not %r" % (feat_decode,))
     if shard is not None and threads <= 0:
         threads = decode_threads_for(shard[1])
-    nf = _cached_featurizer(vocab_path, label_table, scorer.cfg.name, threads)
+    nf = _cached_featurizer(vocab_path, label_table, scorer.cfg.name, threads, feat_decode=feat_decode)
     records = counts = byte_range = None
     if shard is not None and shard_by == "queries":
         records, counts = tsv_shard(nf, tsv_path, shard[0], shard[1])
@@ -157,10 +186,11 @@ def stream_scores_tsv(scorer, tsv_path, vocab_path, label_table, sen2forest: boo
     th = threading.Thread(target=produce, daemon=True)
     th.start()
     copy_stream = _copy_stream(dev)
-    qids, pids, scores = [], [], []
+    qids, pids, scores, bads = [], [], [], []
     import time
     clock = time.perf_counter
     t_get = t_h2d = t_enq = 0.0                  # host seconds waiting for a decoded batch / for its H2D copy / enqueueing its kernels (``stats``)
+    h2d_bytes = 0
     while True:
         t0 = clock()
         b = q.get()
@@ -174,9 +204,13 @@ def stream_scores_tsv(scorer, tsv_path, vocab_path, label_table, sen2forest: boo
         with torch.cuda.stream(copy_stream):
             d = {k: (torch.from_numpy(v).to(dev, non_blocking=True) if isinstance(v, np.ndarray) and v.dtype.kind in "fiu" else v)
                  for k, v in b.items() if k not in ("query_id", "product_id", "keep")}
+        h2d_bytes += sum(t.numel() * t.element_size() for t in d.values() if torch.is_tensor(t))
         t0 = clock()
         copy_stream.synchronize()        # the pinned set may be refilled from here on; the main stream is still busy with batch i
         t1 = clock()
+        if feat_decode == "device":      # on the scoring stream, in front of the scorer's kernels: no host thread waits for it
+            d[_FEAT_KEY[scorer.cfg.name]], bad = decode_features(d, dev)
+            bads.append(bad)
         _, probs = score_batch(scorer, d)
         t_h2d += t1 - t0
         t_enq += clock() - t1
@@ -188,17 +222,20 @@ def stream_scores_tsv(scorer, tsv_path, vocab_path, label_table, sen2forest: boo
     cat = lambda xs, dt: np.concatenate(xs) if xs else np.zeros(0, dt)
     t0 = clock()
     score = torch.cat(scores).float().cpu().numpy() if scores else np.zeros(0, np.float32)
+    _check_decoded(bads, pids)
     if stats is not None:
-        stats.update(wait_decode_s=t_get, wait_h2d_s=t_h2d, enqueue_s=t_enq, drain_s=clock() - t0, batches=len(scores), featurizer=dict(nf.stats))
+        stats.update(wait_decode_s=t_get, wait_h2d_s=t_h2d, enqueue_s=t_enq, drain_s=clock() - t0, batches=len(scores), featurizer=dict(nf.stats),
+                     h2d_bytes=h2d_bytes)
     if shard is not None:
         return cat(qids, np.int64), cat(pids, np.int64), score, counts
     return cat(qids, np.int64), cat(pids, np.int64), score
 
 
 def predict_tsv_native(scorer, tsv_path, vocab_path, label_table, out_path, sen2forest: bool = False, batch_pairs: int = 32768,
-                       threads: int = 0):
-    """``predict_tsv`` with the native featurizer (libmmfeat), decode / H2D / scoring overlapped -- same scores, same file."""
-    qid, pid, score = stream_scores_tsv(scorer, tsv_path, vocab_path, label_table, sen2forest, batch_pairs, threads)
+                       threads: int = 0, feat_decode: str = "host"):
+    """``predict_tsv`` with the native featurizer (libmmfeat), decode / H2D / scoring overlapped -- same scores, same file
+    (``feat_decode``: see ``stream_scores_tsv``)."""
+    qid, pid, score = stream_scores_tsv(scorer, tsv_path, vocab_path, label_table, sen2forest, batch_pairs, threads, feat_decode=feat_decode)
     (scorefile.write_score_csv if scorer.cfg.name == "lxmert" else scorefile.write_score_tsv)(out_path, qid, pid, score)
     return qid, pid, score
 
@@ -258,17 +295,23 @@ class EnsembleScorer:
         pid = np.array([r.product_id for r in rec], np.int64)
         return qid, pid, cat(merged, np.float64), tuple(cat(x, np.float32) for x in parts)
 
-    def score_tsv_native(self, tsv_path, vocab_path, label_table, batch_pairs: int = 16384, threads: int = 0):
+    def score_tsv_native(self, tsv_path, vocab_path, label_table, batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host"):
         """``score_lines`` on a TSV file through libmmfeat, decode and scoring overlapped: a producer thread decodes span batch i+1
         three times (zk flavour, zk with the sen2forest rewrite, lxmert flavour; ctypes releases the GIL, each featurizer rotates
-        three pinned buffer sets) while the main thread copies batch i to the device and runs the ONE fused call on it."""
+        three pinned buffer sets) while the main thread copies batch i to the device and runs the ONE fused call on it.
+        ``feat_decode="device"``: the zk-flavour pass gathers the features' base64 text and the GPU decodes it on the scoring stream in front of
+        the fused call (``stream_scores_tsv``); same scores, a bad record raises ValueError before the pass returns."""
         import queue
         import threading
 
-        # (kept between calls like stream_scores_tsv's; the fused feed reads the 2048-d features from the first pass only, the other two flavours skip their decode)
-        nf_zk = _cached_featurizer(vocab_path, label_table, "zk", threads)
-        nf_s2f = _cached_featurizer(vocab_path, label_table, "zk", threads, want_feats=False, slot=1)
-        nf_lx = _cached_featurizer(vocab_path, label_table, "lxmert", threads, want_feats=False)
+        from .featurizer_native import FEAT_TEXT_KEYS, decode_features
+        if feat_decode not in ("host", "device"):
+            raise ValueError("feat_decode must be 'host' or 'device', not %r" % (feat_decode,))
+        # (kept between calls like stream_scores_tsv's; the fused feed reads the 2048-d features from the first pass only, the other two flavours skip their decode;
+        # fetched so that none of the three can evict another)
+        nf_zk = _cached_featurizer(vocab_path, label_table, "zk", threads, feat_decode=feat_decode)
+        nf_s2f = _cached_featurizer(vocab_path, label_table, "zk", threads, want_feats=False, slot=1, protect=(nf_zk,))
+        nf_lx = _cached_featurizer(vocab_path, label_table, "lxmert", threads, want_feats=False, protect=(nf_zk, nf_s2f))
         q = queue.Queue(maxsize=1)          # one decoded batch waiting + one being decoded + one being scored = 3 buffer sets
 
         def produce():
@@ -288,7 +331,7 @@ class EnsembleScorer:
         import torch
         dev = self.zk.device
         copy_stream = _copy_stream(dev)
-        qids, pids, merged, members = [], [], [], []
+        qids, pids, merged, members, bads = [], [], [], [], []
         while True:
             item = q.get()
             if item is None:
@@ -300,10 +343,22 @@ class EnsembleScorer:
             pids.append(pi)
             # as in stream_scores_tsv: H2D of batch i + 1 on a copy stream while the fused call of batch i runs; nothing waits for the kernels until the end
             with torch.cuda.stream(copy_stream):
-                prep = self.fused.prepare(ensemble_feed(zf, sf, lf))
+                if feat_decode == "device":
+                    feed = {k: (torch.from_numpy(v).to(dev, non_blocking=True) if isinstance(v, np.ndarray) else v)
+                            for k, v in ensemble_feed(zf, sf, lf).items()}
+                    text = {k: torch.from_numpy(zf[k]).to(dev, non_blocking=True) for k in FEAT_TEXT_KEYS}
+                else:
+                    prep = self.fused.prepare(ensemble_feed(zf, sf, lf))
             copy_stream.synchronize()           # the pinned sets of this batch may be refilled from here on
+            if feat_decode == "device":         # the decode on the scoring stream in front of the fused call
+                feed["feats"], bad = decode_features(text, dev)
+                bads.append(bad)
+                prep = self.fused.prepare(feed)
+                held = list(feed.values()) + list(text.values())
+            else:
+                held = list(prep[2].values())
             m, mem = self.fused.score_prepared(prep)
-            for t in prep[2].values():          # allocated on the copy stream, consumed on the main one
+            for t in held:                      # allocated on the copy stream, consumed on the main one
                 if torch.is_tensor(t):
                     t.record_stream(torch.cuda.current_stream(dev))
             merged.append(m)
@@ -314,4 +369,5 @@ class EnsembleScorer:
             return cat(qids, np.int64), cat(pids, np.int64), np.zeros(0, np.float64), tuple(np.zeros(0, np.float32) for _ in range(4))
         mem_all = torch.cat(members, 1).cpu().numpy()
         merged_all = torch.cat(merged).double().cpu().numpy()
+        _check_decoded(bads, pids)
         return cat(qids, np.int64), cat(pids, np.int64), merged_all, tuple(mem_all[k] for k in range(4))

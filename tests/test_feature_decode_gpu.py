@@ -1,0 +1,211 @@
+"""GPU suite: the device feature decode (mms_decode_feats_b64, csrc/featdecode.hip) against libmmfeat's host decoder, bit for bit, and the
+TSV drivers with feat_decode="device" against feat_decode="host" (pipeline.stream_scores_tsv / predict_tsv_native /
+EnsembleScorer.score_tsv_native)."""
+import numpy as np
+import pytest
+import torch
+
+from helpers import small_cfg
+from test_feature_text_gather import TABLE, VOCAB, random_records
+from kddcup_2020_multimodalitiesrecall_2nd_place_amd import featurizer_native as N
+from kddcup_2020_multimodalitiesrecall_2nd_place_amd import lib, pipeline, scorers, weights
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda", 0)
+
+
+def _joined(lines, prefix=b""):
+    enc = [l.encode() for l in lines]
+    offsets = np.zeros(len(enc) + 1, np.int64)
+    np.cumsum([len(e) for e in enc], out=offsets[1:])
+    return prefix + b"".join(enc), offsets + len(prefix)
+
+
+def _host_feats(lines, prefix=b""):
+    data, offsets = _joined(lines, prefix)
+    return N.NativeFeaturizer(VOCAB, TABLE, "zk", threads=4).featurize_bytes(data, offsets)["feats"]
+
+
+def _text_batch(lines, prefix=b""):
+    data, offsets = _joined(lines, prefix)
+    a = N.NativeFeaturizer(VOCAB, TABLE, "zk", threads=4, feat_decode="device").featurize_bytes(data, offsets)
+    return {k: torch.from_numpy(np.array(a[k])).to(DEV) for k in N.FEAT_TEXT_KEYS}, a
+
+
+def _device_feats(lines, prefix=b""):
+    t, _ = _text_batch(lines, prefix)
+    feats, bad = N.decode_features(t)
+    torch.cuda.synchronize()
+    return feats.cpu().numpy(), bad.cpu().numpy()
+
+
+def _decode_raw(chars, off, rows, out):
+    bad = torch.full((rows.shape[0],), 7, dtype=torch.int32, device=DEV)
+    rc = lib.load().mms_decode_feats_b64(chars.data_ptr(), off.data_ptr(), rows.data_ptr(), rows.shape[0], out.data_ptr(), bad.data_ptr(),
+                                         torch.cuda.current_stream().cuda_stream)
+    assert rc == 0
+    torch.cuda.synchronize()
+    return bad.cpu().numpy()
+
+
+@pytest.mark.parametrize("n,prefix", [(1, b""), (7, b"x"), (2500, b"abc")])
+def test_decode_is_bit_exact_with_the_host_decoder(n, prefix):
+    """Random uint32 bit patterns (NaN payloads, infinities, denormals); num_boxes 0 .. 14 = every residue of 8192 n mod 3 and truncation past
+    10 rows; records at odd byte positions of the source text."""
+    nbs = [3] if n == 1 else np.random.default_rng(n).permutation(max(n, 15)) % 15
+    lines = random_records(n, 100 + n, bits=True, nbs=nbs)
+    want = _host_feats(lines, prefix)
+    got, bad = _device_feats(lines, prefix)
+    assert got.shape == want.shape == (n, 10, 2048)
+    assert not bad.any()
+    assert np.array_equal(got.view(np.int32), want.view(np.int32))
+    assert np.isnan(want).any() and np.isinf(want).any() or n < 100
+
+
+def test_stale_output_padding_is_zeroed():
+    lines = random_records(15, 21, bits=True, nbs=list(range(15)))
+    t, a = _text_batch(lines, b"zz")
+    out = torch.full((15, 10, 2048), -1, dtype=torch.int32, device=DEV).view(torch.float32)      # 0xFF bytes everywhere
+    bad = _decode_raw(t["feat_chars"], t["feat_char_off"], t["feat_rows"], out)
+    assert not bad.any()
+    assert np.array_equal(out.cpu().numpy().view(np.int32), _host_feats(lines, b"zz").view(np.int32))
+    # a misaligned start: nothing is read, the record is flagged, its row zeroed, the others untouched
+    off = t["feat_char_off"].clone()
+    off[4] += 8
+    out.fill_(float("nan"))
+    bad = _decode_raw(t["feat_chars"], off, t["feat_rows"], out)
+    assert bad.tolist() == [int(i == 4) for i in range(15)]
+    got = out.cpu().numpy()
+    assert not got[4].view(np.int32).any()
+    keep = [i for i in range(15) if i != 4]
+    assert np.array_equal(got[keep].view(np.int32), _host_feats(lines, b"zz")[keep].view(np.int32))
+
+
+def _corrupt(line, pos, ch):
+    f = line.split("\t")
+    f[5] = f[5][:pos] + ch + f[5][pos + len(ch.encode()):]          # same byte length: the payload size check still passes
+    return "\t".join(f)
+
+
+def _host_accepts(line):
+    try:
+        _host_feats([line])
+        return True
+    except ValueError as e:
+        assert "base64" in str(e)
+        return False
+
+
+def test_validation_matches_the_host():
+    nbs = [1, 2, 3, 12, 4, 10, 5, 3]                              # the last record: 3 rows = 32768 characters, flush with the 16-byte padding
+    lines = random_records(len(nbs), 33, nbs=nbs)
+    need = [(min(n, 10) * 32768 + 2) // 3 for n in nbs]
+    bad_lines = list(lines)
+    bad_lines[0] = _corrupt(lines[0], need[0] - 1, "!")           # the last character the decoder reads (a partial unit)
+    bad_lines[1] = _corrupt(lines[1], 17, "=")                    # '=' inside the needed range
+    bad_lines[3] = _corrupt(lines[3], need[3] + 4000, "!")        # inside row 11: ignored by both decoders
+    bad_lines[5] = _corrupt(lines[5], 0, "\u00e9")                # non-ASCII bytes
+    bad_lines[7] = _corrupt(lines[7], need[7] - 1, "*")           # the buffer's very last character
+    expect = [1, 1, 0, 0, 0, 1, 0, 1]
+    feats, bad = _device_feats(bad_lines, b"q")
+    assert bad.tolist() == expect
+    assert [int(not _host_accepts(l)) for l in bad_lines] == expect  # the host featurizer rejects exactly the flagged records
+    good = [i for i in range(len(nbs)) if not expect[i]]
+    want = _host_feats([bad_lines[i] for i in good])
+    assert np.array_equal(feats[good].view(np.int32), want.view(np.int32))
+    t, a = _text_batch(bad_lines, b"q")
+    assert t["feat_chars"].numel() == a["feat_char_off"][-1] + need[-1]          # no slack behind the last record
+
+
+def test_abi_argument_checks():
+    l = lib.load()
+    st = torch.cuda.current_stream().cuda_stream
+    assert l.mms_decode_feats_b64(None, None, None, 0, None, None, st) == 0
+    x = torch.zeros(64, dtype=torch.int64, device=DEV)
+    p = x.data_ptr()
+    assert l.mms_decode_feats_b64(p, p, p, -1, p, p, st) != 0 and b"B must be" in l.mms_global_error()
+    assert l.mms_decode_feats_b64(None, p, p, 1, p, p, st) != 0 and b"null" in l.mms_global_error()
+    assert l.mms_decode_feats_b64(p, p, p, 1, p, None, st) != 0
+    assert l.mms_decode_feats_b64(p + 4, p, p, 1, p, p, st) != 0 and b"aligned" in l.mms_global_error()
+    torch.cuda.synchronize()
+    assert not x.any()                                            # nothing ran
+
+
+def _tsv(tmp_path, lines, name="valid.tsv"):
+    p = tmp_path / name
+    body = "product_id\timage_h\timage_w\tnum_boxes\tboxes\tfeatures\tclass_labels\tquery\tquery_id\n"
+    body += "".join(l + ("\n\n" if i % 9 == 4 else "\n") for i, l in enumerate(lines))
+    p.write_text(body, encoding="utf-8")
+    return str(p)
+
+
+@pytest.mark.parametrize("name", ["zk", "lds", "lxmert"])
+def test_stream_scores_device_equals_host(tmp_path, name):
+    lines = random_records(61, 7)
+    path = _tsv(tmp_path, lines)
+    cfg = small_cfg(name)
+    s = scorers.make_scorer(cfg, weights.make_weights(cfg))
+    try:
+        kw = dict(batch_pairs=16, ramp=4, threads=3)
+        st_h, st_d = {}, {}
+        qh, ph, sh = pipeline.stream_scores_tsv(s, path, VOCAB, TABLE, stats=st_h, **kw)
+        qd, pd, sd = pipeline.stream_scores_tsv(s, path, VOCAB, TABLE, stats=st_d, feat_decode="device", **kw)
+        assert len(sh) == 61 and st_d["batches"] > 2
+        assert np.array_equal(qh, qd) and np.array_equal(ph, pd) and np.array_equal(sh.view(np.int32), sd.view(np.int32))
+        assert st_d["h2d_bytes"] < st_h["h2d_bytes"]
+        for r in range(2):                                        # a rank's shard
+            got = pipeline.stream_scores_tsv(s, path, VOCAB, TABLE, shard=(r, 2), feat_decode="device", **kw)
+            want = pipeline.stream_scores_tsv(s, path, VOCAB, TABLE, shard=(r, 2), **kw)
+            assert 0 < len(got[2]) < 61
+            assert all(np.array_equal(x, y) for x, y in zip(got[:3], want[:3])) and got[3] == want[3]
+    finally:
+        s.close()
+
+
+def test_predict_tsv_native_writes_the_same_file(tmp_path):
+    lines = random_records(23, 8)
+    path = _tsv(tmp_path, lines)
+    cfg = small_cfg("zk")
+    s = scorers.make_scorer(cfg, weights.make_weights(cfg))
+    try:
+        pipeline.predict_tsv_native(s, path, VOCAB, TABLE, str(tmp_path / "h.txt"), batch_pairs=8)
+        pipeline.predict_tsv_native(s, path, VOCAB, TABLE, str(tmp_path / "d.txt"), batch_pairs=8, feat_decode="device")
+    finally:
+        s.close()
+    assert (tmp_path / "h.txt").read_bytes() == (tmp_path / "d.txt").read_bytes()
+
+
+def test_ensemble_device_equals_host(tmp_path):
+    lines = random_records(37, 12)
+    path = _tsv(tmp_path, lines)
+    cfgs = {n: small_cfg(n) for n in ("zk", "lds", "lxmert")}
+    sc = {n: scorers.make_scorer(c, weights.make_weights(c)) for n, c in cfgs.items()}
+    try:
+        ens = pipeline.EnsembleScorer(sc["zk"], sc["lds"], sc["lxmert"])
+        qh, ph, mh, parts_h = ens.score_tsv_native(path, VOCAB, TABLE, batch_pairs=8)
+        qd, pd, md, parts_d = ens.score_tsv_native(path, VOCAB, TABLE, batch_pairs=8, feat_decode="device")
+        qh2, _, mh2, _ = ens.score_tsv_native(path, VOCAB, TABLE, batch_pairs=8)       # host and device featurizers cached side by side
+    finally:
+        for s in sc.values():
+            s.close()
+    assert len(mh) == 37 and np.array_equal(qh, qd) and np.array_equal(ph, pd)
+    assert np.array_equal(mh, md) and all(np.array_equal(x, y) for x, y in zip(parts_h, parts_d))
+    assert np.array_equal(mh, mh2)
+
+
+def test_corrupted_record_raises_naming_it(tmp_path):
+    lines = random_records(30, 14, nbs=[2, 3, 4])
+    bad = _corrupt(lines[17], 100, "!")
+    pid = int(bad.split("\t")[0])
+    path = _tsv(tmp_path, lines[:17] + [bad] + lines[18:])
+    cfg = small_cfg("zk")
+    s = scorers.make_scorer(cfg, weights.make_weights(cfg))
+    try:
+        with pytest.raises(ValueError, match=r"record 17 of the pass \(product_id %d\): bad base64" % pid):
+            pipeline.stream_scores_tsv(s, path, VOCAB, TABLE, batch_pairs=8, ramp=0, feat_decode="device")
+        with pytest.raises(ValueError, match="base64"):
+            pipeline.stream_scores_tsv(s, path, VOCAB, TABLE, batch_pairs=8, ramp=0)
+        ok = pipeline.stream_scores_tsv(s, _tsv(tmp_path, lines, "ok.tsv"), VOCAB, TABLE, batch_pairs=8, feat_decode="device")
+        assert len(ok[2]) == 30
+    finally:
+        s.close()

@@ -1,6 +1,7 @@
 """End-to-end TSV -> scores throughput (SURVEY.md section 8(f) row 2 + the hot path): synthetic valid/testB-like TSV file,
 native featurizer threads -> pinned buffers -> H2D on a copy stream -> scorer, all overlapped (pipeline.stream_scores_tsv).
-usage (GPU box): python tools/e2e_tsv_bench.py [records] [model] [decode threads, comma list (0 = library default)]"""
+usage (GPU box): python tools/e2e_tsv_bench.py [records] [model] [decode threads, comma list (0 = library default)] [--feat-decode host|device]
+(--feat-decode device: the features' base64 text is gathered on the host and decoded on the GPU; the H2D bytes per record are printed beside pairs/s)"""
 import os
 import sys
 import time
@@ -14,6 +15,11 @@ from kddcup_2020_multimodalitiesrecall_2nd_place_amd import featurizer as F, pip
 from kddcup_2020_multimodalitiesrecall_2nd_place_amd.config import LdsConfig, LxmertConfig, ZkConfig  # noqa: E402
 from kddcup_2020_multimodalitiesrecall_2nd_place_amd.featurizer_native import NativeFeaturizer  # noqa: E402
 
+feat_decode = "host"
+if "--feat-decode" in sys.argv:
+    k_ = sys.argv.index("--feat-decode")
+    feat_decode = sys.argv[k_ + 1]
+    del sys.argv[k_:k_ + 2]
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 30000
 name = sys.argv[2] if len(sys.argv) > 2 else "zk"
 threads_list = [int(t) for t in sys.argv[3].split(",")] if len(sys.argv) > 3 else [0]
@@ -41,33 +47,33 @@ if name == "ensemble":      # BASELINE.json config 5: TSV -> four score tables -
     ens = pipeline.EnsembleScorer(sc["zk"], sc["lds"], sc["lxmert"])
     for _ in range(3):
         torch.cuda.synchronize(); t0 = time.time()
-        qid, pid, merged, parts = ens.score_tsv_native(path, VOCAB, TABLE, batch_pairs=16384)
+        qid, pid, merged, parts = ens.score_tsv_native(path, VOCAB, TABLE, batch_pairs=16384, feat_decode=feat_decode)
         t1 = time.time()
         rows = E.submission_rows(qid, pid, merged)          # uniqueness filter + top-5 (main.py:64-104) on the three arrays
         E.write_submission("/tmp/e2e_submission.csv", rows)
         dt = time.time() - t0
-    print("TSV -> 4 score tables -> submission.csv: %.0f pairs/s end to end (%d pairs, %d queries; scoring %.2f s, post-process %.2f s)"
-          % (len(merged) / dt, len(merged), len(rows), t1 - t0, dt - (t1 - t0)), flush=True)
+    print("TSV -> 4 score tables -> submission.csv, feat_decode %s: %.0f pairs/s end to end (%d pairs, %d queries; scoring %.2f s, post-process %.2f s)"
+          % (feat_decode, len(merged) / dt, len(merged), len(rows), t1 - t0, dt - (t1 - t0)), flush=True)
     os.remove(path)
     sys.exit(0)
 cfg = {"zk": ZkConfig(), "lds": LdsConfig(), "lxmert": LxmertConfig()}[name]
 sc = scorers.make_scorer(cfg, weights.make_weights(cfg), device=0)
 for th in threads_list:
-    nf = NativeFeaturizer(VOCAB, TABLE, name, threads=th, pinned=True, reuse_buffers=True, pools=3)
+    nf = NativeFeaturizer(VOCAB, TABLE, name, threads=th, pinned=True, reuse_buffers=True, pools=3, feat_decode=feat_decode)
     for _ in range(3):
         nf.stats.clear()
         t0 = time.time(); k = sum(len(b["query_id"]) for b in nf.iter_file(path, 8192)); dt = time.time() - t0
-    print("featurizer alone (%s of %d host threads): %.0f records/s, %.2f GB/s of TSV  [ms: %s]" % (
-        th or "default", os.cpu_count(), k / dt, os.path.getsize(path) / dt / 1e9, ", ".join("%s %.0f" % (a_, b_ * 1e3) for a_, b_ in nf.stats.items())), flush=True)
+    print("featurizer alone (%s of %d host threads, feat_decode %s): %.0f records/s, %.2f GB/s of TSV  [ms: %s]" % (
+        th or "default", os.cpu_count(), feat_decode, k / dt, os.path.getsize(path) / dt / 1e9, ", ".join("%s %.0f" % (a_, b_ * 1e3) for a_, b_ in nf.stats.items())), flush=True)
     nf.close()
     for bp in (8192, 16384):
         for _ in range(3):
             torch.cuda.synchronize(); t0 = time.time()
             stt = {}
-            qid, pid, score = pipeline.stream_scores_tsv(sc, path, VOCAB, TABLE, batch_pairs=bp, threads=th, stats=stt)
+            qid, pid, score = pipeline.stream_scores_tsv(sc, path, VOCAB, TABLE, batch_pairs=bp, threads=th, stats=stt, feat_decode=feat_decode)
             torch.cuda.synchronize(); dt = time.time() - t0
-        print("TSV -> scores, batch %d, threads %s: %.0f pairs/s (%d pairs, %.2f s)  [host ms: waiting for a decoded batch %.0f, for H2D %.0f, enqueueing %.0f, final drain %.0f; %d batches]"
-              % (bp, th or "default", len(score) / dt, len(score), dt, stt["wait_decode_s"] * 1e3, stt["wait_h2d_s"] * 1e3, stt["enqueue_s"] * 1e3, stt["drain_s"] * 1e3, stt["batches"]), flush=True)
+        print("TSV -> scores, feat_decode %s, batch %d, threads %s: %.0f pairs/s (%d pairs, %.2f s), H2D %.1f KB/record  [host ms: waiting for a decoded batch %.0f, for H2D %.0f, enqueueing %.0f, final drain %.0f; %d batches]"
+              % (feat_decode, bp, th or "default", len(score) / dt, len(score), dt, stt["h2d_bytes"] / max(len(score), 1) / 1e3, stt["wait_decode_s"] * 1e3, stt["wait_h2d_s"] * 1e3, stt["enqueue_s"] * 1e3, stt["drain_s"] * 1e3, stt["batches"]), flush=True)
 # device-resident rate of the same records (the ceiling of the lines above): the batches of the file, already on the device
 nf = NativeFeaturizer(VOCAB, TABLE, name, pinned=False)
 dev_batches = []
