@@ -141,7 +141,7 @@ class NativeFeaturizer:
                                            never_split=F.SPECIALS if hf else ())
         self.threads, self.pinned = threads, pinned
         self.stats = {}                                   # seconds per stage, accumulated by iter_spans / _run
-        self.prefault = True                              # iter_spans maps a batch's pages in parallel before splitting it (mmf_prefault)
+        self.prefault = True                              # iter_spans' default: map a batch's pages in parallel before splitting it (mmf_prefault)
         self._h = C.c_void_p()
         if self.lib.mmf_create(vocab_path.encode(), 100 if hf else 200, int(hf), C.byref(self._h)) != 0:
             raise RuntimeError("mmf_create: " + self.lib.mmf_last_error().decode())
@@ -260,16 +260,12 @@ class NativeFeaturizer:
         """query_id of every record of a TSV file, in file order (int64), without decoding a record: line split + the last field.  A rank of
         an N-GPU job finds its contiguous query block of a shared file with it (``pipeline.tsv_shard``)."""
         out = []
-        save, self.prefault = self.prefault, False                # heads and tails only: nothing worth mapping ahead, nothing to release
-        try:
-            for base, _g, starts, ends in self.iter_spans(path, 1 << 16):
-                q = np.empty(len(starts), np.int64)
-                rc = self.lib.mmf_query_ids(base, starts.ctypes.data, ends.ctypes.data, len(starts), q.ctypes.data)
-                if rc != 0:
-                    raise ValueError("mmf_query_ids failed (%d): %s" % (rc, self.lib.mmf_last_error().decode()))
-                out.append(q)
-        finally:
-            self.prefault = save
+        for base, _g, starts, ends in self.iter_spans(path, 1 << 16, prefault=False):      # heads and tails only: nothing worth mapping ahead
+            q = np.empty(len(starts), np.int64)
+            rc = self.lib.mmf_query_ids(base, starts.ctypes.data, ends.ctypes.data, len(starts), q.ctypes.data)
+            if rc != 0:
+                raise ValueError("mmf_query_ids failed (%d): %s" % (rc, self.lib.mmf_last_error().decode()))
+            out.append(q)
         return np.concatenate(out) if out else np.zeros(0, np.int64)
 
     def byte_shard(self, path: str, rank: int, world: int):
@@ -311,15 +307,15 @@ class NativeFeaturizer:
             finally:
                 del view
 
-    def iter_spans(self, path: str, batch_lines: int = 8192, ramp: int = 0, records=None, byte_range=None):
+    def iter_spans(self, path: str, batch_lines: int = 8192, ramp: int = 0, records=None, byte_range=None, prefault=None):
         """Stream a TSV file as record spans: yields (base address, getbytes, starts, ends) per ``batch_lines`` records
         (blank lines and header lines containing 'product_id' skipped, kdd_data.py:70-71).  ``ramp`` > 0: the first batches hold
         ramp, 2 ramp, 4 ramp ... records until ``batch_lines`` is reached -- a consumer that overlaps decode, copy and scoring starts
         after the decode of ``ramp`` records instead of a whole batch (pipeline.stream_scores_tsv).  ``records = (lo, hi)``: only the records
         lo <= index < hi of the file (header and blank lines not counted) are yielded -- a rank's shard; the ones in front are split, not decoded.
         ``byte_range = (b0, b1)`` (``byte_shard``): only the records that start in [b0, b1), without touching the rest of the file.  The file is mmapped and the line
-        splitting is native; the spans stay valid until the generator is advanced.  ``self.stats`` accumulates the seconds spent
-        mapping / unmapping, prefaulting and splitting (tools/feat_bench.py prints them)."""
+        splitting is native; the spans stay valid until the generator is advanced.  ``prefault``: map each batch's pages ahead (None: ``self.prefault``).
+        ``self.stats`` accumulates the seconds spent mapping / unmapping, prefaulting and splitting (tools/feat_bench.py prints them)."""
         import mmap
         import time
         st = self.stats
@@ -342,7 +338,7 @@ class NativeFeaturizer:
                 seen, (rec_lo, rec_hi) = 0, (records if records is not None else (0, 1 << 62))
                 skip_buf = None
                 mapped, per_rec = pos, 64 << 10              # bytes of the mapping whose pages are in, estimate of a record's size
-                prefault = self.prefault and hasattr(self.lib, "mmf_prefault")
+                prefault = (self.prefault if prefault is None else prefault) and hasattr(self.lib, "mmf_prefault")
                 while pos < size and seen < rec_hi:
                     if seen < rec_lo:                         # records of other ranks in front of this shard: find their ends, touch nothing else
                         if skip_buf is None:
@@ -386,13 +382,18 @@ class NativeFeaturizer:
 
     def iter_file(self, path: str, batch_lines: int = 8192, sen2forest: bool = False, layout: bool = True, ramp: int = 0, records=None, byte_range=None):
         """Stream a TSV file: yields one batch dict per ``batch_lines`` records (see ``iter_spans``)."""
-        for base, getbytes, starts, ends in self.iter_spans(path, batch_lines, ramp, records, byte_range):
-            a = self._run(base, getbytes, starts, ends, sen2forest)
-            yield self._layout(a) if layout else a
+        for span in self.iter_spans(path, batch_lines, ramp, records, byte_range):
+            yield self.featurize_spans(*span, sen2forest) if layout else self._run(*span, sen2forest)
+
+    def featurize_spans(self, base, getbytes, starts, ends, sen2forest: bool = False) -> dict:
+        """One span batch of ``iter_spans`` -> the model's batch layout."""
+        return self._layout(self._run(base, getbytes, starts, ends, sen2forest))
 
     # ---- the three reference batch layouts (same keys / dtypes as featurizer.*_batch) ----
     def batch(self, lines, sen2forest: bool = False) -> dict:
         return self._layout(self.featurize(lines, sen2forest))
+
+    FEAT_KEY = {"zk": "np_images_features", "lds": "features", "lxmert": "feats"}     # the box features' key in each layout
 
     def _layout(self, a: dict) -> dict:
         n, T = a["product_id"].shape[0], self.text_len

@@ -5,12 +5,18 @@ The written files are what ``ensemble.ensemble`` (main.py's merge) consumes.
 """
 from __future__ import annotations
 
+import contextlib
 import os
+import queue
+import threading
+import time
 
 import numpy as np
+import torch
 
 from . import featurizer as F
 from . import scorefile
+from .featurizer_native import FEAT_TEXT_KEYS, NativeFeaturizer, decode_features
 from .scorers import score_batch
 
 
@@ -61,50 +67,138 @@ def kdd_predict(scorer, tsv_lines, label_table, tokenizer, save_path=None, batch
 
 _FEATURIZERS: dict = {}                  # key -> NativeFeaturizer, least recently used first
 _FEATURIZER_CACHE = 6
+_BUSY: set = set()                       # keys of the cached featurizers that a pass holds
+_CACHE_LOCK = threading.Lock()
 _COPY_STREAMS: dict = {}
 
 
 def _copy_stream(dev):
     """ONE H2D stream per device for the life of the process: torch's caching allocator keeps a pool per stream, so a fresh stream per call would reserve
     a fresh set of batch buffers per call (2.6 GB per pass of stream_scores_tsv, never reused: tools/soak_tsv.py)."""
-    import torch
     key = (dev.type, dev.index)
     if key not in _COPY_STREAMS:
         _COPY_STREAMS[key] = torch.cuda.Stream(dev)
     return _COPY_STREAMS[key]
 
 
-def _cached_featurizer(vocab_path, label_table, model, threads, want_feats=True, slot=0, feat_decode="host", protect=()):
-    """One NativeFeaturizer (helper threads + three pinned buffer sets, ~2 GB at 8192-record batches) per (vocabulary, label table, model,
-    threads, feature decode mode): creating them costs about as much as decoding 30 000 records.  At most ``_FEATURIZER_CACHE`` are kept; a miss
-    closes the least recently used one, never one of ``protect`` (the featurizers a caller has fetched for the same pass)."""
-    from .featurizer_native import NativeFeaturizer
-    key = (os.path.abspath(vocab_path), os.path.getmtime(vocab_path), model, threads, want_feats, slot, feat_decode,
-           tuple(sorted((int(k), v) for k, v in label_table.items())))
-    nf = _FEATURIZERS.pop(key, None)
-    if nf is None:
-        victims = [k for k, v in _FEATURIZERS.items() if not any(v is p for p in protect)]
-        while len(_FEATURIZERS) >= _FEATURIZER_CACHE and victims:
-            _FEATURIZERS.pop(victims.pop(0)).close()
-        nf = NativeFeaturizer(vocab_path, label_table, model, threads=threads, pinned=True, reuse_buffers=True, pools=3, want_feats=want_feats,
-                              feat_decode=feat_decode)
-    _FEATURIZERS[key] = nf               # (re)inserted last: the most recently used
-    return nf
+@contextlib.contextmanager
+def _lease(vocab_path, label_table, threads, *specs):
+    """-> the NativeFeaturizers of ``specs`` ((model, want_feats, feat_decode) each), busy until the block ends, by an exception or not.  One is
+    cached per (vocabulary, label table, model, threads, want_feats, feat_decode) -- helper threads + three pinned buffer sets, ~2 GB at 8192-record
+    batches, as costly to make as decoding 30 000 records --, at most ``_FEATURIZER_CACHE``, the least recently used evicted first.  A busy one is
+    never evicted nor handed out twice: a busy key, or a miss with no idle entry to evict, gets a private featurizer, closed when the block ends."""
+    labels = tuple(sorted((int(k), v) for k, v in label_table.items()))
+    held = []                            # (featurizer, its cache key or None: a private one)
+    try:
+        with _CACHE_LOCK:
+            for model, want_feats, feat_decode in specs:
+                key = (os.path.abspath(vocab_path), os.path.getmtime(vocab_path), model, threads, want_feats, feat_decode, labels)
+                nf = None if key in _BUSY else _FEATURIZERS.pop(key, None)
+                if nf is None:
+                    idle = [] if key in _BUSY else [k for k in _FEATURIZERS if k not in _BUSY]
+                    for k in idle[:max(0, len(_FEATURIZERS) + 1 - _FEATURIZER_CACHE)]:     # make room, least recently used first
+                        _FEATURIZERS.pop(k).close()
+                    nf = NativeFeaturizer(vocab_path, label_table, model, threads=threads, pinned=True, reuse_buffers=True, pools=3,
+                                          want_feats=want_feats, feat_decode=feat_decode)
+                cached = key not in _BUSY and len(_FEATURIZERS) < _FEATURIZER_CACHE
+                if cached:
+                    _FEATURIZERS[key] = nf       # (re)inserted last: the most recently used
+                    _BUSY.add(key)
+                held.append((nf, key if cached else None))
+        yield [nf for nf, _ in held]
+    finally:
+        with _CACHE_LOCK:
+            for nf, key in held:
+                if key is None:
+                    nf.close()
+                _BUSY.discard(key)
 
 
-_FEAT_KEY = {"zk": "np_images_features", "lds": "features", "lxmert": "feats"}     # the features' key in each model's batch layout
+@contextlib.contextmanager
+def _background(source):
+    """``with _background(source) as items: for x in items: ...`` -- ``source`` (an iterable) runs on a producer thread one item ahead of the
+    consumer (a depth-1 queue: one item waiting, one being produced, one being consumed -- the featurizers' three buffer sets); a producer error
+    is raised in the consumer.  However the block ends, the producer is told to stop, the queue drained and the thread joined; ``source``'s
+    iterator is closed on the producer thread (a generator's ``finally`` runs there: ``iter_spans`` unmaps its file)."""
+    q, stop, it, end = queue.Queue(maxsize=1), threading.Event(), iter(source), object()
+
+    def produce():
+        try:
+            for x in it:
+                q.put(x)
+                if stop.is_set():
+                    return
+            q.put(end)
+        except BaseException as e:       # surfaced in the consumer
+            q.put(e)
+        finally:
+            getattr(it, "close", lambda: None)()
+
+    def consume():
+        while (x := q.get()) is not end:
+            if isinstance(x, BaseException):
+                raise x
+            yield x
+
+    th = threading.Thread(target=produce, daemon=True)
+    th.start()
+    try:
+        yield consume()
+    finally:
+        stop.set()
+        while th.is_alive():             # unblock a pending put until the producer has seen the stop
+            with contextlib.suppress(queue.Empty):
+                q.get(timeout=0.01)
+        th.join()
 
 
-def _check_decoded(bads, pids):
-    """feat_decode="device": the per-batch ``bad`` flags of the pass (device tensors, one read-back) -> ValueError naming the first bad record."""
-    import torch
-    if not bads:
-        return
-    hit = torch.nonzero(torch.cat(bads)).flatten()
-    if hit.numel():
-        i = int(hit[0])
+def _overlapped_pass(batches, dev, feat_key, score):
+    """The three overlapped stages of the file-fed drivers (``stream_scores_tsv``).  ``batches`` (run by ``_background``): (query_id copy,
+    product_id copy, dict of host arrays) per batch; a dict with ``FEAT_TEXT_KEYS`` gets ``decode_features``' output under ``feat_key``;
+    ``score(device dict)`` enqueues the batch's kernels.  -> (query_id, product_id, [score(d) per batch], stats); raises on a bad device-decoded
+    record.  However the pass ends, the producer has stopped and the copy stream is synchronised before this returns or raises."""
+    copy_stream = _copy_stream(dev)
+    clock = time.perf_counter
+    qids, pids, outs, bads = [], [], [], []
+    t_get = t_h2d = t_enq = 0.0          # host seconds waiting for a decoded batch / for its H2D copy / enqueueing its kernels
+    h2d_bytes = 0
+    with _background(batches) as items:
+        try:
+            while True:
+                t0 = clock()
+                item = next(items, None)
+                t_get += clock() - t0
+                if item is None:
+                    break
+                qids.append(item[0])
+                pids.append(item[1])
+                with torch.cuda.stream(copy_stream):
+                    d = {k: (torch.from_numpy(v).to(dev, non_blocking=True) if isinstance(v, np.ndarray) and v.dtype.kind in "fiu" else v)
+                         for k, v in item[2].items()}
+                h2d_bytes += sum(t.numel() * t.element_size() for t in d.values() if torch.is_tensor(t))
+                t0 = clock()
+                copy_stream.synchronize()    # the pinned set may be refilled from here on; the scoring stream is still busy with the previous batch
+                t1 = clock()
+                for t in d.values():         # allocated on the copy stream, consumed on the scoring one: defer reuse of the memory
+                    if torch.is_tensor(t):
+                        t.record_stream(torch.cuda.current_stream(dev))
+                if FEAT_TEXT_KEYS[0] in d:   # on the scoring stream, in front of the scorer's kernels: no host thread waits for it
+                    d[feat_key], bad = decode_features(d, dev)
+                    bads.append(bad)
+                outs.append(score(d))
+                t_h2d += t1 - t0
+                t_enq += clock() - t1
+        finally:
+            copy_stream.synchronize()        # no DMA still reads a pinned set when the featurizer goes back to the cache
+    t0 = clock()
+    torch.cuda.current_stream(dev).synchronize()
+    hit = torch.nonzero(torch.cat(bads)).flatten().tolist() if bads else []         # the device decode's per-batch bad flags, one read-back
+    if hit:
         raise ValueError("record %d of the pass (product_id %d): bad base64 in features (decoded on the device; %d bad record(s))"
-                         % (i, int(np.concatenate(pids)[i]), hit.numel()))
+                         % (hit[0], int(np.concatenate(pids)[hit[0]]), len(hit)))
+    cat = lambda xs: np.concatenate(xs) if xs else np.zeros(0, np.int64)
+    return cat(qids), cat(pids), outs, dict(wait_decode_s=t_get, wait_h2d_s=t_h2d, enqueue_s=t_enq, drain_s=clock() - t0, batches=len(outs),
+                                            h2d_bytes=h2d_bytes)
 
 
 def tsv_shard(nf, tsv_path, rank: int, world: int):
@@ -156,79 +250,29 @@ def stream_scores_tsv(scorer, tsv_path, vocab_path, label_table, sen2forest: boo
     the scorer's kernels.  Scores are bit-identical to the host mode's; a record whose text is not base64 raises ValueError (naming it) before
     the pass returns.
     """
-    import queue
-    import threading
-
-    import torch
-
-    from .featurizer_native import decode_features
     if feat_decode not in ("host", "device"):
         raise ValueError("feat_decode must be 'host' or 'device', not %r" % (feat_decode,))
     if shard is not None and threads <= 0:
         threads = decode_threads_for(shard[1])
-    nf = _cached_featurizer(vocab_path, label_table, scorer.cfg.name, threads, feat_decode=feat_decode)
-    records = counts = byte_range = None
-    if shard is not None and shard_by == "queries":
-        records, counts = tsv_shard(nf, tsv_path, shard[0], shard[1])
-    elif shard is not None:
-        byte_range = nf.byte_shard(tsv_path, shard[0], shard[1])
-    dev = scorer.device
-    q = queue.Queue(maxsize=1)           # one decoded batch waiting + one being decoded + one being copied = 3 pools
+    with _lease(vocab_path, label_table, threads, (scorer.cfg.name, True, feat_decode)) as (nf,):
+        before = dict(nf.stats)
+        records = counts = byte_range = None
+        if shard is not None and shard_by == "queries":
+            records, counts = tsv_shard(nf, tsv_path, shard[0], shard[1])
+        elif shard is not None:
+            byte_range = nf.byte_shard(tsv_path, shard[0], shard[1])
 
-    def produce():
-        try:
+        def batches():
             for b in nf.iter_file(tsv_path, batch_pairs, sen2forest, ramp=ramp, records=records, byte_range=byte_range):
-                q.put(b)
-            q.put(None)
-        except BaseException as e:       # surfaced in the consumer
-            q.put(e)
+                yield b.pop("query_id").copy(), b.pop("product_id").copy(), b
 
-    th = threading.Thread(target=produce, daemon=True)
-    th.start()
-    copy_stream = _copy_stream(dev)
-    qids, pids, scores, bads = [], [], [], []
-    import time
-    clock = time.perf_counter
-    t_get = t_h2d = t_enq = 0.0                  # host seconds waiting for a decoded batch / for its H2D copy / enqueueing its kernels (``stats``)
-    h2d_bytes = 0
-    while True:
-        t0 = clock()
-        b = q.get()
-        t_get += clock() - t0
-        if b is None:
-            break
-        if isinstance(b, BaseException):
-            raise b
-        qids.append(b["query_id"].copy())
-        pids.append(b["product_id"].copy())
-        with torch.cuda.stream(copy_stream):
-            d = {k: (torch.from_numpy(v).to(dev, non_blocking=True) if isinstance(v, np.ndarray) and v.dtype.kind in "fiu" else v)
-                 for k, v in b.items() if k not in ("query_id", "product_id", "keep")}
-        h2d_bytes += sum(t.numel() * t.element_size() for t in d.values() if torch.is_tensor(t))
-        t0 = clock()
-        copy_stream.synchronize()        # the pinned set may be refilled from here on; the main stream is still busy with batch i
-        t1 = clock()
-        if feat_decode == "device":      # on the scoring stream, in front of the scorer's kernels: no host thread waits for it
-            d[_FEAT_KEY[scorer.cfg.name]], bad = decode_features(d, dev)
-            bads.append(bad)
-        _, probs = score_batch(scorer, d)
-        t_h2d += t1 - t0
-        t_enq += clock() - t1
-        for t in d.values():             # allocated on the copy stream, consumed on the main one: defer reuse of the memory
-            if torch.is_tensor(t):
-                t.record_stream(torch.cuda.current_stream(dev))
-        scores.append(probs[:, 1])
-    th.join()
-    cat = lambda xs, dt: np.concatenate(xs) if xs else np.zeros(0, dt)
-    t0 = clock()
-    score = torch.cat(scores).float().cpu().numpy() if scores else np.zeros(0, np.float32)
-    _check_decoded(bads, pids)
-    if stats is not None:
-        stats.update(wait_decode_s=t_get, wait_h2d_s=t_h2d, enqueue_s=t_enq, drain_s=clock() - t0, batches=len(scores), featurizer=dict(nf.stats),
-                     h2d_bytes=h2d_bytes)
+        qid, pid, probs, st = _overlapped_pass(batches(), scorer.device, nf.FEAT_KEY[nf.model], lambda d: score_batch(scorer, d)[1][:, 1])
+        score = torch.cat(probs).float().cpu().numpy() if probs else np.zeros(0, np.float32)
+        if stats is not None:
+            stats.update(st, featurizer={k: v - before.get(k, 0.0) for k, v in nf.stats.items()})
     if shard is not None:
-        return cat(qids, np.int64), cat(pids, np.int64), score, counts
-    return cat(qids, np.int64), cat(pids, np.int64), score
+        return qid, pid, score, counts
+    return qid, pid, score
 
 
 def predict_tsv_native(scorer, tsv_path, vocab_path, label_table, out_path, sen2forest: bool = False, batch_pairs: int = 32768,
@@ -301,73 +345,19 @@ class EnsembleScorer:
         three pinned buffer sets) while the main thread copies batch i to the device and runs the ONE fused call on it.
         ``feat_decode="device"``: the zk-flavour pass gathers the features' base64 text and the GPU decodes it on the scoring stream in front of
         the fused call (``stream_scores_tsv``); same scores, a bad record raises ValueError before the pass returns."""
-        import queue
-        import threading
-
-        from .featurizer_native import FEAT_TEXT_KEYS, decode_features
         if feat_decode not in ("host", "device"):
             raise ValueError("feat_decode must be 'host' or 'device', not %r" % (feat_decode,))
-        # (kept between calls like stream_scores_tsv's; the fused feed reads the 2048-d features from the first pass only, the other two flavours skip their decode;
-        # fetched so that none of the three can evict another)
-        nf_zk = _cached_featurizer(vocab_path, label_table, "zk", threads, feat_decode=feat_decode)
-        nf_s2f = _cached_featurizer(vocab_path, label_table, "zk", threads, want_feats=False, slot=1, protect=(nf_zk,))
-        nf_lx = _cached_featurizer(vocab_path, label_table, "lxmert", threads, want_feats=False, protect=(nf_zk, nf_s2f))
-        q = queue.Queue(maxsize=1)          # one decoded batch waiting + one being decoded + one being scored = 3 buffer sets
+        # (kept between calls like stream_scores_tsv's; the fused feed reads the 2048-d features from the first pass only, the other two flavours skip their decode)
+        with _lease(vocab_path, label_table, threads, ("zk", True, feat_decode), ("zk", False, "host"), ("lxmert", False, "host")) as (nf_zk, nf_s2f, nf_lx):
 
-        def produce():
-            try:
-                for base, getbytes, starts, ends in nf_zk.iter_spans(tsv_path, batch_pairs, ramp=1024):      # (ramp: the first fused call starts after 1024 records)
-                    a = nf_zk._run(base, getbytes, starts, ends, False)
-                    item = (a["query_id"].copy(), a["product_id"].copy(), nf_zk._layout(a),
-                            nf_s2f._layout(nf_s2f._run(base, getbytes, starts, ends, True)),
-                            nf_lx._layout(nf_lx._run(base, getbytes, starts, ends, False)))
-                    q.put(item)
-                q.put(None)
-            except BaseException as e:      # surfaced in the consumer
-                q.put(e)
+            def batches():
+                for span in nf_zk.iter_spans(tsv_path, batch_pairs, ramp=1024):      # (ramp: the first fused call starts after 1024 records)
+                    zf = nf_zk.featurize_spans(*span)
+                    feed = ensemble_feed(zf, nf_s2f.featurize_spans(*span, True), nf_lx.featurize_spans(*span))
+                    yield zf["query_id"].copy(), zf["product_id"].copy(), {**feed, **{k: zf[k] for k in FEAT_TEXT_KEYS if k in zf}}
 
-        th = threading.Thread(target=produce, daemon=True)
-        th.start()
-        import torch
-        dev = self.zk.device
-        copy_stream = _copy_stream(dev)
-        qids, pids, merged, members, bads = [], [], [], [], []
-        while True:
-            item = q.get()
-            if item is None:
-                break
-            if isinstance(item, BaseException):
-                raise item
-            qi, pi, zf, sf, lf = item
-            qids.append(qi)
-            pids.append(pi)
-            # as in stream_scores_tsv: H2D of batch i + 1 on a copy stream while the fused call of batch i runs; nothing waits for the kernels until the end
-            with torch.cuda.stream(copy_stream):
-                if feat_decode == "device":
-                    feed = {k: (torch.from_numpy(v).to(dev, non_blocking=True) if isinstance(v, np.ndarray) else v)
-                            for k, v in ensemble_feed(zf, sf, lf).items()}
-                    text = {k: torch.from_numpy(zf[k]).to(dev, non_blocking=True) for k in FEAT_TEXT_KEYS}
-                else:
-                    prep = self.fused.prepare(ensemble_feed(zf, sf, lf))
-            copy_stream.synchronize()           # the pinned sets of this batch may be refilled from here on
-            if feat_decode == "device":         # the decode on the scoring stream in front of the fused call
-                feed["feats"], bad = decode_features(text, dev)
-                bads.append(bad)
-                prep = self.fused.prepare(feed)
-                held = list(feed.values()) + list(text.values())
-            else:
-                held = list(prep[2].values())
-            m, mem = self.fused.score_prepared(prep)
-            for t in held:                      # allocated on the copy stream, consumed on the main one
-                if torch.is_tensor(t):
-                    t.record_stream(torch.cuda.current_stream(dev))
-            merged.append(m)
-            members.append(mem)
-        th.join()
-        cat = lambda xs, dt: np.concatenate(xs) if xs else np.zeros(0, dt)
-        if not merged:
-            return cat(qids, np.int64), cat(pids, np.int64), np.zeros(0, np.float64), tuple(np.zeros(0, np.float32) for _ in range(4))
-        mem_all = torch.cat(members, 1).cpu().numpy()
-        merged_all = torch.cat(merged).double().cpu().numpy()
-        _check_decoded(bads, pids)
-        return cat(qids, np.int64), cat(pids, np.int64), merged_all, tuple(mem_all[k] for k in range(4))
+            qid, pid, out, _ = _overlapped_pass(batches(), self.zk.device, "feats", lambda d: self.fused.score_prepared(self.fused.prepare(d)))
+        if not out:
+            return qid, pid, np.zeros(0, np.float64), tuple(np.zeros(0, np.float32) for _ in range(4))
+        mem_all = torch.cat([mem for _, mem in out], 1).cpu().numpy()
+        return qid, pid, torch.cat([m for m, _ in out]).double().cpu().numpy(), tuple(mem_all[k] for k in range(4))

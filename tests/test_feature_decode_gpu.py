@@ -209,3 +209,81 @@ def test_corrupted_record_raises_naming_it(tmp_path):
         assert len(ok[2]) == 30
     finally:
         s.close()
+
+
+@pytest.mark.parametrize("feat_decode", ["host", "device"])
+def test_stream_pass_that_raises_leaves_the_cached_featurizer_clean(tmp_path, monkeypatch, feat_decode):
+    """A scorer error on the second batch: stream_scores_tsv raises, and the next pass on the same cached featurizer gives the bits of a clean pass
+    (the producer was stopped, its buffer sets and the copy stream idle before the featurizer went back to the cache)."""
+    path = _tsv(tmp_path, random_records(61, 9))
+    cfg = small_cfg("zk")
+    s = scorers.make_scorer(cfg, weights.make_weights(cfg))
+    kw = dict(batch_pairs=8, ramp=0, threads=3, feat_decode=feat_decode)
+    try:
+        want = pipeline.stream_scores_tsv(s, path, VOCAB, TABLE, **kw)
+        calls, real = [], pipeline.score_batch
+
+        def failing(scorer, d):
+            calls.append(1)
+            if len(calls) == 2:
+                raise RuntimeError("scorer failed mid-pass")
+            return real(scorer, d)
+        monkeypatch.setattr(pipeline, "score_batch", failing)
+        with pytest.raises(RuntimeError, match="mid-pass"):
+            pipeline.stream_scores_tsv(s, path, VOCAB, TABLE, **kw)
+        monkeypatch.setattr(pipeline, "score_batch", real)
+        assert not pipeline._BUSY
+        got = pipeline.stream_scores_tsv(s, path, VOCAB, TABLE, **kw)
+    finally:
+        s.close()
+    assert len(want[2]) == 61 and np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+    assert np.array_equal(got[2].view(np.int32), want[2].view(np.int32))
+
+
+def test_ensemble_pass_that_raises_leaves_the_cached_featurizers_clean(tmp_path):
+    path = _tsv(tmp_path, random_records(37, 13))
+    cfgs = {n: small_cfg(n) for n in ("zk", "lds", "lxmert")}
+    sc = {n: scorers.make_scorer(c, weights.make_weights(c)) for n, c in cfgs.items()}
+    try:
+        ens = pipeline.EnsembleScorer(sc["zk"], sc["lds"], sc["lxmert"])
+        for mode in ("host", "device"):
+            want = ens.score_tsv_native(path, VOCAB, TABLE, batch_pairs=4, feat_decode=mode)
+            calls, real = [], ens.fused.score_prepared
+
+            def failing(prep):
+                calls.append(1)
+                if len(calls) == 2:
+                    raise RuntimeError("fused call failed mid-pass")
+                return real(prep)
+            ens.fused.score_prepared = failing
+            with pytest.raises(RuntimeError, match="mid-pass"):
+                ens.score_tsv_native(path, VOCAB, TABLE, batch_pairs=4, feat_decode=mode)
+            del ens.fused.score_prepared
+            assert not pipeline._BUSY
+            got = ens.score_tsv_native(path, VOCAB, TABLE, batch_pairs=4, feat_decode=mode)
+            assert len(want[2]) == 37 and np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+            assert np.array_equal(got[2], want[2]) and all(np.array_equal(x.view(np.int32), y.view(np.int32)) for x, y in zip(got[3], want[3]))
+    finally:
+        for s in sc.values():
+            s.close()
+
+
+def test_stream_stats_report_the_featurizer_seconds_of_their_own_pass(tmp_path, monkeypatch):
+    monkeypatch.setattr(pipeline, "_FEATURIZERS", {})
+    monkeypatch.setattr(pipeline, "_BUSY", set())
+    path = _tsv(tmp_path, random_records(40, 10))
+    cfg = small_cfg("lds")
+    s = scorers.make_scorer(cfg, weights.make_weights(cfg))
+    st1, st2 = {}, {}
+    try:
+        pipeline.stream_scores_tsv(s, path, VOCAB, TABLE, batch_pairs=8, threads=2, stats=st1)
+        pipeline.stream_scores_tsv(s, path, VOCAB, TABLE, batch_pairs=8, threads=2, stats=st2, shard=(1, 2), shard_by="queries")
+    finally:
+        s.close()
+    (nf,) = pipeline._FEATURIZERS.values()
+    assert set(st1["featurizer"]) <= set(nf.stats) and set(st2["featurizer"]) == set(nf.stats) and "decode" in st1["featurizer"]
+    for k, total in nf.stats.items():
+        assert st1["featurizer"].get(k, 0.0) >= 0 and st2["featurizer"][k] >= 0
+        assert st1["featurizer"].get(k, 0.0) + st2["featurizer"][k] == pytest.approx(total, rel=1e-9, abs=1e-12)
+        assert st2["featurizer"][k] < total or st1["featurizer"].get(k, 0.0) == 0
+    nf.close()

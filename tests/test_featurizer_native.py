@@ -323,3 +323,39 @@ print("PASSES_OK", len(ref))
     next(spans); next(spans)                                    # two batches handed out, the first one's range queued ...
     assert nf.lib.mmf_release_later(nf._h, None, 0) >= 1       # ... (this is what used to survive the unmap)
     spans.close()
+
+
+def test_background_pass_cleans_up_when_the_consumer_raises(tmp_path):
+    """pipeline._background (the producer thread of the TSV drivers): a consumer that raises after the first batch leaves no producer thread, no
+    mapping of the file and no pending release range behind -- the source generator is closed on the producer thread (iter_spans' finally)."""
+    import threading
+    from kddcup_2020_multimodalitiesrecall_2nd_place_amd import pipeline
+    p = tmp_path / "pass.tsv"
+    p.write_bytes(("\n".join(_random_lines(400, 56)) + "\n").encode("utf-8"))
+    nf = N.NativeFeaturizer(VOCAB, TABLE, "zk", threads=2, reuse_buffers=True, pools=3)
+    maps = lambda: open("/proc/self/maps").read()
+    threads = threading.active_count()
+
+    def batches():
+        for b in nf.iter_file(str(p), 64, ramp=16):
+            yield b.pop("query_id").copy(), b.pop("product_id").copy(), b
+    with pytest.raises(RuntimeError, match="consumer"):
+        with pipeline._background(batches()) as items:
+            for i, (qid, pid, b) in enumerate(items):
+                assert len(qid) == 16 and str(p) in maps()
+                raise RuntimeError("consumer")
+    assert threading.active_count() == threads
+    assert str(p) not in maps()
+    assert nf.lib.mmf_release_later(nf._h, None, 0) == 0
+    # a producer error reaches the consumer, after the batches before it; a complete pass sees every batch
+    def failing():
+        yield 1
+        raise ValueError("producer")
+    with pytest.raises(ValueError, match="producer"):
+        with pipeline._background(failing()) as items:
+            assert next(items) == 1
+            next(items)
+    with pipeline._background(batches()) as items:
+        assert sum(len(q) for q, _, _ in items) == 400
+    assert threading.active_count() == threads and str(p) not in maps()
+    nf.close()
