@@ -72,7 +72,9 @@ typedef struct mms_config {
                                  arbitrary fp32 checkpoint to ~2e-5; 4: fp8 (OCP e4m3) weights with one fp32 scale per output
                                  channel and fp8 activations on the four big encoder GEMM classes (QKV, attention output,
                                  FFN up / down), fp8 MFMA -- BASELINE.json config 5; OUTSIDE the 1e-3 logit contract, its measured
-                                 deviation is reported by the tests and bench.py */
+                                 deviation is reported by the tests and bench.py.  The fp8 activation stores SATURATE: beyond +-448,
+                                 infinities included, the largest finite code -- and a NaN becomes -448 (the clamp in front of the
+                                 conversion drops it), so a NaN that arises inside a precision-4 forward is not visible in its logits */
     int32_t chunk_pairs;      /* max pairs per internal launch wave (0 = default 32768); a batch is cut into equal chunks */
     int32_t stop_after;       /* debug: run only the first n encoder layers (-1 = all) and skip nothing else */
     int32_t device;           /* HIP device ordinal */
@@ -327,6 +329,44 @@ int mms_dbg_qkv_attn(const float* x, int64_t rows1, int64_t rows2, const int32_t
  * anything else: -1 */
 int64_t mms_dbg_counter(mms_handle* h, int32_t which);
 int mms_dbg_layernorm(const float* x, const float* gamma, const float* beta, int64_t M, float* out_f32, void* stream);
+/* ONE launch of the small-sequence attention kernel (attn.hip) in the forms the forwards use.  q / k / v: device fp32, already in the layout `flags` names; B pairs;
+ * Sq / Sk: the MAXIMUM tokens of a pair (tile selection, <= 48); q_rows / kv_rows: rows of the two streams.  q_off / q_cnt, kv_off / kv_cnt: int32 [B] first row and
+ * live tokens of every pair (1 <= cnt <= S, rows inside the stream: checked on the host), or NULL = dense (row b * S, S tokens).  key_add: additive key mask by
+ * kv-stream row, or NULL.  flags:
+ *   bit 0  head-major operands: q = 12 blocks [q_rows][64], k and v = 12 blocks [kv_rows][64] each (the [Q | K | V] blocks of a forward's projection buffer);
+ *          else row-major [rows][768]
+ *   bit 1  reverse: the last pair first
+ *   bit 2  CLS-only (the last layer before the pooler): q is a compact row-major [B][768] whatever bit 0 says, Sq == 1, q_rows == B, no q_off; output row b
+ *   bit 3  the context leaves as e4m3 bytes (precision 4) instead of the split planes
+ * out_f32 [q_rows (bit 2: B)][768]: the planes, or the decoded bytes; both are zero-filled before the launch, so a row no live query owns comes back 0 */
+int mms_dbg_attention_ex(const float* q, const float* k, const float* v, int64_t B, int32_t Sq, int32_t Sk, int64_t q_rows, int64_t kv_rows,
+                         const int32_t* q_off, const int32_t* q_cnt, const int32_t* kv_off, const int32_t* kv_cnt, const float* key_add,
+                         int32_t flags, float* out_f32, void* stream);
+/* ONE pack plan (rowops.hip) of n pairs with T text tokens, its raw tables written to the caller's device buffers.  kind:
+ *   0  zk, the one-block route (n <= 1024)          in_a = len_query int32 [n], in_b = num_boxes int32 [n]
+ *   1  zk, the three-launch route (token + box plan) same inputs
+ *   2  lds                                           in_a = features fp32 [n][10][2048], in_b = labelfeat int64 [n][10][8]
+ *   3  lxmert, both streams                          in_a = input_mask int64 [n][T], in_b = visual_attention_mask fp32 [n][10]
+ *   4  lxmert, language stream only                  in_a = input_mask; in_b ignored
+ * off / cnt [n], tok_src / key_add [n * (tokens of a dense pair)]: the token plan (lxmert: the language stream); rows_dev[0] = its live rows.
+ * off2 / cnt2 [n], src2 [n * 10]: kinds 0, 1 the box plan, kind 3 the vision stream (with add2 [n * 10]); rows_dev[1] = its live rows.  Kind 2: src2 (optional)
+ * receives the "box has a non-zero feature" flags [n * 10].  Kind 4 does not touch the second table */
+int mms_dbg_pack_plan(int32_t kind, int64_t n, int32_t T, const void* in_a, const void* in_b, int32_t* off, int32_t* cnt, int32_t* tok_src, float* key_add,
+                      int32_t* off2, int32_t* cnt2, int32_t* src2, float* add2, int32_t* rows_dev, void* stream);
+/* ONE de-duplication (batchops.hip) with a workspace sized as a forward sizes it (hash table: the smallest power of two >= max(1024, 2 * rows)).  kind 0: label
+ * tuples int32 [rows][8]; 1: int64 [rows][8]; 2: lxmert queries, ids / mask int64 [rows][T].  *count_out (host) = distinct keys; index [rows]; kinds 0, 1: uniq32 /
+ * uniq64 [rows][8] (either may be NULL); kind 2: rows_of [rows], the first row of every distinct query */
+int mms_dbg_dedup(int32_t kind, const void* ids, const int64_t* mask, int32_t T, int64_t rows, int32_t* count_out, int32_t* index, int32_t* uniq32,
+                  int64_t* uniq64, int32_t* rows_of, void* stream);
+/* the LayerNorm kernel with the fields mms_dbg_layernorm leaves at their defaults: out = LN(x + resid[r_index ? r_index[row] : row]).  resid_f32 [resid_rows][768] or
+ * NULL; r_index int32 [M] (entries in [0, resid_rows): checked on the host) or NULL; m_live >= 0: the device-side row count (rows >= min(M, m_live) are not
+ * written), < 0: none.  flags: bit 0 reverse, bit 1 also write the row as e4m3 bytes (decoded to out_f8 [M][768]), bit 2 the skip word is set (nothing is
+ * written).  The planes and the bytes are zero-filled first */
+int mms_dbg_layernorm_ex(const float* x, const float* gamma, const float* beta, int64_t M, const float* resid_f32, int64_t resid_rows, const int32_t* r_index,
+                         int64_t m_live, int32_t flags, float* out_f32, float* out_f8, void* stream);
+/* one conversion launcher on n elements (n % 32 == 0).  kind 0: fp32 -> e4m3 bytes; 1: e4m3 bytes -> fp32; 2: fp32 -> split planes -> fp32 (round trip);
+ * 3: fp32 -> split planes -> e4m3 bytes */
+int mms_dbg_convert(int32_t kind, const void* in, void* out, int64_t n, void* stream);
 #endif /* MMS_TEST_HOOKS */
 
 #ifdef __cplusplus

@@ -2661,4 +2661,171 @@ int mms_dbg_layernorm(const float* x, const float* gamma, const float* beta, int
     return MMS_OK;
 }
 
+// ---- hooks of the ragged attention, plan, de-duplication and row kernels: the launch forms the forwards use (att_block, last_block_cls, the pack plans) ----
+// device buffers of one hook call, freed on every way out
+struct DbgPool {
+    std::vector<void*> p;
+    ~DbgPool() { for (void* q : p) (void)hipFree(q); }
+    void* get(size_t bytes) {
+        void* q = nullptr;
+        if (hipMalloc(&q, bytes ? bytes : 4) != hipSuccess) return nullptr;
+        p.push_back(q);
+        return q;
+    }
+};
+// per-pair rows of a ragged stream, checked on the host before a kernel reads through them: 1 <= cnt <= S, [off, off + cnt) inside the stream
+static bool dbg_pairs_ok(const int32_t* off_dev, const int32_t* cnt_dev, int64_t B, int S, int64_t rows) {
+    std::vector<int32_t> off((size_t)B), cnt((size_t)B);
+    if (hipMemcpy(off.data(), off_dev, (size_t)B * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    if (hipMemcpy(cnt.data(), cnt_dev, (size_t)B * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
+    for (int64_t b = 0; b < B; ++b)
+        if (cnt[b] < 1 || cnt[b] > S || off[b] < 0 || (int64_t)off[b] + cnt[b] > rows) return false;
+    return true;
+}
+
+int mms_dbg_attention_ex(const float* q, const float* k, const float* v, int64_t B, int32_t Sq, int32_t Sk, int64_t q_rows, int64_t kv_rows,
+                         const int32_t* q_off, const int32_t* q_cnt, const int32_t* kv_off, const int32_t* kv_cnt, const float* key_add,
+                         int32_t flags, float* out_f32, void* stream) {
+    const bool hm = flags & 1, cls = flags & 4, f8 = flags & 8;
+    if (!q || !k || !v || !out_f32 || B <= 0 || B > (1 << 20) || Sq <= 0 || Sk <= 0 || Sq > 48 || Sk > 48 || q_rows <= 0 || kv_rows <= 0 || (flags & ~15) ||
+        (q_off == nullptr) != (q_cnt == nullptr) || (kv_off == nullptr) != (kv_cnt == nullptr) || (cls && (Sq != 1 || q_off || q_rows != B))) {
+        g_err = "mms_dbg_attention_ex: bad argument"; return MMS_ERR_ARG;
+    }
+    if ((q_off ? !dbg_pairs_ok(q_off, q_cnt, B, Sq, q_rows) : (!cls && B * Sq > q_rows)) || (kv_off ? !dbg_pairs_ok(kv_off, kv_cnt, B, Sk, kv_rows) : B * Sk > kv_rows)) {
+        g_err = "mms_dbg_attention_ex: a pair's rows lie outside its stream"; return MMS_ERR_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t out_rows = cls ? B : q_rows, n = out_rows * H;
+    DbgPool pool;
+    bf16* op = (bf16*)pool.get((size_t)n * 4);
+    unsigned char* o8 = (unsigned char*)pool.get((size_t)n);
+    if (!op || !o8) return dbg_fail("mms_dbg_attention_ex: hipMalloc");
+    DBG_TRY(hipMemsetAsync(op, 0, (size_t)n * 4, st));
+    DBG_TRY(hipMemsetAsync(o8, 0, (size_t)n, st));
+    AttnParams a{};
+    a.q = q; a.k = k; a.v = v;
+    if (cls) { a.ldq = H; a.hs_q = MMS_HEAD_DIM; a.q_stride = 1; a.o_compact = 1; }                    // last_block_cls
+    else if (hm) { a.ldq = MMS_HEAD_DIM; a.hs_q = q_rows * MMS_HEAD_DIM; }                            // attn_q
+    else { a.ldq = H; a.hs_q = MMS_HEAD_DIM; }
+    if (hm) { a.ldkv = MMS_HEAD_DIM; a.hs_kv = kv_rows * MMS_HEAD_DIM; }                              // attn_kv
+    else { a.ldkv = H; a.hs_kv = MMS_HEAD_DIM; }
+    a.q_base = 0; a.Sq = Sq; a.kv_base = 0; a.Sk = Sk; a.key_add = key_add;
+    a.o_hi = op; a.o_lo = op + MMS_PLANE_LO; a.ldo = H; a.B = (int)B;
+    a.q_off = (const int*)q_off; a.q_cnt = (const int*)q_cnt; a.kv_off = (const int*)kv_off; a.kv_cnt = (const int*)kv_cnt;
+    a.reverse = (flags & 2) ? 1 : 0;
+    if (f8) a.o_f8 = o8;
+    if (!launch_attention(a, st)) { g_err = "mms_dbg_attention_ex: no kernel for this (Sq, Sk)"; return MMS_ERR_ARG; }
+    if (f8) launch_f8_to_f32(o8, out_f32, n, st);
+    else launch_planes_to_f32(op, op + MMS_PLANE_LO, out_f32, n, st);
+    DBG_TRY(hipStreamSynchronize(st));
+    DBG_TRY(hipGetLastError());
+    return MMS_OK;
+}
+
+int mms_dbg_pack_plan(int32_t kind, int64_t n, int32_t T, const void* in_a, const void* in_b, int32_t* off, int32_t* cnt, int32_t* tok_src, float* key_add,
+                      int32_t* off2, int32_t* cnt2, int32_t* src2, float* add2, int32_t* rows_dev, void* stream) {
+    const bool two = kind == 0 || kind == 1 || kind == 3;
+    if (kind < 0 || kind > 4 || n <= 0 || n > (1 << 22) || T <= 0 || T > 32 || !in_a || (kind != 4 && !in_b) || !off || !cnt || !tok_src || !key_add || !rows_dev ||
+        (two && (!off2 || !cnt2 || !src2)) || (kind == 3 && !add2)) { g_err = "mms_dbg_pack_plan: bad argument"; return MMS_ERR_ARG; }
+    hipStream_t st = (hipStream_t)stream;
+    DbgPool pool;
+    if (kind == 0) {
+        if (!launch_zk_plans_small((const int*)in_a, (const int*)in_b, T, (int)n, cnt2, off2, src2, cnt, off, tok_src, key_add, rows_dev, st)) {
+            g_err = "mms_dbg_pack_plan: the one-block zk plan takes at most 1024 pairs"; return MMS_ERR_ARG;
+        }
+    } else if (kind == 1) {
+        launch_zk_box_plan((const int*)in_a, (const int*)in_b, T, (int)n, cnt2, off2, src2, rows_dev + 1, st);
+        launch_zk_pack_plan((const int*)in_a, (const int*)in_b, T, (int)n, off, cnt, tok_src, key_add, rows_dev, st);
+    } else if (kind == 2) {
+        int* nz = src2 ? src2 : (int*)pool.get((size_t)n * MMS_NBOX * 4);      // the not-all-zero flags come back when the caller asks for them
+        if (!nz) return dbg_fail("mms_dbg_pack_plan: hipMalloc");
+        launch_lds_pack_plan((const float*)in_a, (const int64_t*)in_b, T, (int)n, nz, off, cnt, tok_src, key_add, rows_dev, st);
+    } else {
+        launch_lx_pack_plan((const int64_t*)in_a, kind == 3 ? (const float*)in_b : nullptr, T, (int)n, off, cnt, tok_src, key_add, rows_dev,
+                            off2, cnt2, src2, add2, rows_dev + 1, st);
+    }
+    DBG_TRY(hipStreamSynchronize(st));
+    DBG_TRY(hipGetLastError());
+    return MMS_OK;
+}
+
+int mms_dbg_dedup(int32_t kind, const void* ids, const int64_t* mask, int32_t T, int64_t rows, int32_t* count_out, int32_t* index, int32_t* uniq32,
+                  int64_t* uniq64, int32_t* rows_of, void* stream) {
+    if (kind < 0 || kind > 2 || !ids || rows <= 0 || rows > ((int64_t)1 << 24) || !count_out || !index || (kind == 2 && (!mask || !rows_of || T <= 0))) {
+        g_err = "mms_dbg_dedup: bad argument"; return MMS_ERR_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    int cap = 1024;      // ensure_dedup_ws / lxmert's lq_cap: the smallest power of two >= max(1024, 2 * rows)
+    while (cap < 2 * rows) cap <<= 1;
+    DbgPool pool;
+    int* slots = (int*)pool.get((size_t)cap * (kind == 2 ? 2 : 1) * 4);
+    int* rep = (int*)pool.get((size_t)rows * 4);
+    int* uid = (int*)pool.get((size_t)rows * 4);
+    int* counter = (int*)pool.get(16);
+    if (!slots || !rep || !uid || !counter) return dbg_fail("mms_dbg_dedup: hipMalloc");
+    if (kind == 0) launch_label_dedup_i32((const int32_t*)ids, (int)rows, slots, cap, rep, uid, counter, uniq32, uniq64, index, st);
+    else if (kind == 1) launch_label_dedup_i64((const int64_t*)ids, (int)rows, slots, cap, rep, uid, counter, uniq32, uniq64, index, st);
+    else launch_query_dedup((const int64_t*)ids, mask, T, (int)rows, slots, cap, rep, uid, counter, rows_of, index, st);
+    DBG_TRY(hipMemcpyAsync(count_out, counter, 4, hipMemcpyDeviceToHost, st));
+    DBG_TRY(hipStreamSynchronize(st));
+    DBG_TRY(hipGetLastError());
+    return MMS_OK;
+}
+
+int mms_dbg_layernorm_ex(const float* x, const float* gamma, const float* beta, int64_t M, const float* resid_f32, int64_t resid_rows, const int32_t* r_index,
+                         int64_t m_live, int32_t flags, float* out_f32, float* out_f8, void* stream) {
+    const bool f8 = flags & 2;
+    if (!x || !gamma || !beta || !out_f32 || M <= 0 || M > (1 << 24) || (flags & ~7) || (f8 && !out_f8) || (resid_f32 && resid_rows <= 0) || (r_index && !resid_f32) ||
+        (resid_f32 && !r_index && resid_rows < M)) { g_err = "mms_dbg_layernorm_ex: bad argument"; return MMS_ERR_ARG; }
+    if (r_index) {
+        std::vector<int32_t> ri((size_t)M);
+        DBG_TRY(hipMemcpy(ri.data(), r_index, (size_t)M * 4, hipMemcpyDeviceToHost));
+        for (int32_t r : ri) if (r < 0 || r >= resid_rows) { g_err = "mms_dbg_layernorm_ex: r_index outside the residual"; return MMS_ERR_ARG; }
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t n = M * H;
+    DbgPool pool;
+    bf16* op = (bf16*)pool.get((size_t)n * 4);
+    unsigned char* o8 = (unsigned char*)pool.get((size_t)n);
+    int* ctl = (int*)pool.get(16);
+    bf16* rp = resid_f32 ? (bf16*)pool.get((size_t)resid_rows * H * 4) : nullptr;
+    if (!op || !o8 || !ctl || (resid_f32 && !rp)) return dbg_fail("mms_dbg_layernorm_ex: hipMalloc");
+    DBG_TRY(hipMemsetAsync(op, 0, (size_t)n * 4, st));
+    DBG_TRY(hipMemsetAsync(o8, 0, (size_t)n, st));
+    const int host_ctl[2] = {(int)m_live, (flags & 4) ? 1 : 0};      // [0] device-side row count, [1] the skip word
+    DBG_TRY(hipMemcpyAsync(ctl, host_ctl, 8, hipMemcpyHostToDevice, st));
+    LnResid r;
+    if (resid_f32) {
+        launch_split_f32(resid_f32, rp, rp + MMS_PLANE_LO, resid_rows * H, st);
+        r.hi = rp; r.lo = rp + MMS_PLANE_LO; r.ld = H; r.r_index = (const int*)r_index;
+    }
+    r.reverse = flags & 1;
+    if (f8) r.o_f8 = o8;
+    r.skip = ctl + 1;
+    launch_ln_to_planes(x, H, gamma, beta, op, op + MMS_PLANE_LO, H, (int)M, st, m_live >= 0 ? ctl : nullptr, r);
+    launch_planes_to_f32(op, op + MMS_PLANE_LO, out_f32, n, st);
+    if (f8) launch_f8_to_f32(o8, out_f8, n, st);
+    DBG_TRY(hipStreamSynchronize(st));
+    DBG_TRY(hipGetLastError());
+    return MMS_OK;
+}
+
+int mms_dbg_convert(int32_t kind, const void* in, void* out, int64_t n, void* stream) {
+    if (kind < 0 || kind > 3 || !in || !out || n <= 0 || n % 32) { g_err = "mms_dbg_convert: bad argument (n % 32)"; return MMS_ERR_ARG; }
+    hipStream_t st = (hipStream_t)stream;
+    DbgPool pool;
+    if (kind == 0) launch_f32_to_f8((const float*)in, (unsigned char*)out, n, st);
+    else if (kind == 1) launch_f8_to_f32((const unsigned char*)in, (float*)out, n, st);
+    else {
+        bf16* pl = (bf16*)pool.get((size_t)n * 4);
+        if (!pl) return dbg_fail("mms_dbg_convert: hipMalloc");
+        launch_split_f32((const float*)in, pl, pl + MMS_PLANE_LO, n, st);
+        if (kind == 2) launch_planes_to_f32(pl, pl + MMS_PLANE_LO, (float*)out, n, st);
+        else launch_planes_to_f8(pl, pl + MMS_PLANE_LO, (unsigned char*)out, n, st);
+    }
+    DBG_TRY(hipStreamSynchronize(st));
+    DBG_TRY(hipGetLastError());
+    return MMS_OK;
+}
+
 }  // extern "C"

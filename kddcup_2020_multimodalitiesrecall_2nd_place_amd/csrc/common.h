@@ -65,6 +65,9 @@ __host__ __device__ __forceinline__ long long wtile_off(long long n, long long k
 
 // fp32 -> OCP e4m3fn, round-to-nearest-even, saturating at +-448 (precision mode 4).  v_cvt_pk_fp8_f32 packs two values into
 // one 16-bit half of a dword; the clamp makes the result independent of the instruction's overflow convention.
+// NaN SATURATES too: fmaxf returns its non-NaN operand, so a NaN leaves as -448 (0xFE), not as the NaN code 0x7F the bare instruction
+// would give (measured; tests/test_row_kernels_gpu.py pins it).  Keeping NaN a NaN would cost the fp8 epilogues a compare + select per
+// value; until that is measured against bench.py's fp8 line, a precision-4 forward cannot report a NaN through its activations.
 __device__ __forceinline__ unsigned pack4_f8(float a, float b, float c, float d) {
     a = fminf(fmaxf(a, -448.f), 448.f); b = fminf(fmaxf(b, -448.f), 448.f);
     c = fminf(fmaxf(c, -448.f), 448.f); d = fminf(fmaxf(d, -448.f), 448.f);

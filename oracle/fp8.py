@@ -5,7 +5,9 @@ There is no reference code for this mode (the reference is fp32 throughout); wha
 (OCP 8-bit floating point, E4M3: 1 sign, 4 exponent bits with bias 7, 3 mantissa bits, no infinities, max finite 448,
 subnormal step 2^-9) and this build's own quantisation rules (csrc/rowops.hip k_quant_rows_f8 / pack4_f8):
 
-* activations: round-to-nearest-even to e4m3, saturating at +-448;
+* activations: round-to-nearest-even to e4m3, saturating at +-448.  The device clamps BEFORE it converts (common.h pack4_f8:
+  fminf(fmaxf(x, -448), 448)), and fmaxf returns its non-NaN operand: a NaN activation SATURATES to -448 on the device, whereas
+  e4m3_round() below lets a NaN through.  The two agree on every number; tests/test_row_kernels_gpu.py pins the device's NaN rule;
 * weights: per output channel, scale = the smallest power of two with max|w| / scale <= 448; bytes = e4m3(w / scale).
 """
 import numpy as np
@@ -23,6 +25,15 @@ def e4m3_round(x):
     step = np.exp2(e - 3.0)
     q = np.rint(a / step) * step          # np.rint rounds half to even; a / step is exact (power-of-two step)
     return s * np.minimum(q, 448.0)
+
+
+def e4m3_decode(codes):
+    """uint8 codes -> float64 values (OCP E4M3: S.EEEE.MMM, bias 7; exponent 0: subnormal m * 2^-9; 0x7F / 0xFF: NaN, no infinities)."""
+    c = np.asarray(codes).astype(np.int64)
+    e, m = (c >> 3) & 15, c & 7
+    v = np.where(e == 0, m * 2.0 ** -9, (1.0 + m / 8.0) * np.exp2(e - 7.0))
+    v = np.where((e == 15) & (m == 7), np.nan, v)
+    return np.where(c & 0x80, -v, v)
 
 
 def quant_weight_rows(w):

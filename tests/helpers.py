@@ -63,6 +63,110 @@ def fp32ckpt_case():
     return g, cfg, w, sd, synth.lxmert_batch(ps, cfg.text_len)
 
 
+# ---- numpy statements of the pack plans (csrc/rowops.hip), written from the models' mask rules, not from the kernels ----
+N_BOX = 10
+
+
+def _pack(keep):
+    """keep [n, S] bool -> (off, cnt, src): the kept tokens in token order, the pairs contiguous in pair order."""
+    cnt = keep.sum(1).astype(np.int64)
+    return np.cumsum(cnt) - cnt, cnt, np.flatnonzero(keep.ravel())
+
+
+def zk_plan_spec(len_query, num_boxes, T):
+    """zk: the keys are sequence_mask(len_query, T) || sequence_mask(num_boxes, 10) (out-of-range lengths clipped), masked keys carry
+    -10000.  A pair keeps its live keys and its CLS row; a pair with no live key keeps all its tokens.  The box plan lists the kept boxes."""
+    lq = np.clip(np.asarray(len_query, np.int64), 0, T)
+    nb = np.clip(np.asarray(num_boxes, np.int64), 0, N_BOX)
+    live = np.concatenate([np.arange(T)[None, :] < lq[:, None], np.arange(N_BOX)[None, :] < nb[:, None]], 1)
+    dense_add = np.where(live, 0.0, -10000.0).astype(np.float32)
+    keep = live.copy()
+    keep[:, 0] = True
+    keep[~live.any(1)] = True
+    off, cnt, src = _pack(keep)
+    b_off, b_cnt, box_idx = _pack(keep[:, T:])
+    return dict(off=off, cnt=cnt, tok_src=src, key_add=dense_add.ravel()[src], rows=int(cnt.sum()), dense_add=dense_add, keep=keep,
+                b_off=b_off, b_cnt=b_cnt, box_idx=box_idx, b_rows=int(b_cnt.sum()))
+
+
+def lds_plan_spec(feats, labelfeat, T):
+    """lds: no mask; T text rows; every box with a feature != 0 is its own row; the boxes whose 2048 features are all zero share the first
+    of them (key_add log(their number)); of the label rows the first box of every distinct 8-tuple stays (key_add log(multiplicity)).
+    key_add comes back as float64."""
+    feats = np.asarray(feats).reshape(-1, N_BOX, 2048)
+    lab = np.asarray(labelfeat, np.int64).reshape(-1, N_BOX, 8)
+    n, S = feats.shape[0], T + 2 * N_BOX
+    keep = np.zeros((n, S), bool)
+    add = np.zeros((n, S), np.float64)
+    keep[:, :T] = True
+    nz = (feats != 0).any(-1)                     # -0.0 == 0; NaN != 0
+    for b in range(n):
+        zeros = np.flatnonzero(~nz[b])
+        keep[b, T:T + N_BOX] = nz[b]
+        if len(zeros):
+            keep[b, T + zeros[0]] = True
+            add[b, T + zeros[0]] = np.log(float(len(zeros)))
+        seen = {}
+        for j in range(N_BOX):
+            seen.setdefault(tuple(int(v) for v in lab[b, j]), []).append(j)
+        for js in seen.values():
+            keep[b, T + N_BOX + js[0]] = True
+            add[b, T + N_BOX + js[0]] = np.log(float(len(js)))
+    off, cnt, src = _pack(keep)
+    return dict(off=off, cnt=cnt, tok_src=src, key_add=add.ravel()[src], rows=int(cnt.sum()), keep=keep, nz=nz)
+
+
+def lx_plan_spec(input_mask, visual_mask, T):
+    """lxmert: additive key term (1 - m) * -10000 in fp32.  The language stream keeps the positions with mask != 0 and position 0, an
+    all-masked pair all T; the vision stream (visual_mask None: absent) keeps the boxes with mask != 0, or all ten."""
+    m = np.asarray(input_mask, np.int64).reshape(-1, T)
+    l_dense = ((np.float32(1.0) - m.astype(np.float32)) * np.float32(-10000.0)).astype(np.float32)
+    keep = m != 0
+    none = ~keep.any(1)
+    keep = keep.copy()
+    keep[:, 0] = True
+    keep[none] = True
+    off, cnt, src = _pack(keep)
+    out = dict(l_off=off, l_cnt=cnt, l_src=src, l_add=l_dense.ravel()[src], l_rows=int(cnt.sum()), l_dense=l_dense, l_keep=keep)
+    if visual_mask is not None:
+        vm = np.asarray(visual_mask, np.float32).reshape(-1, N_BOX)
+        v_dense = ((np.float32(1.0) - vm) * np.float32(-10000.0)).astype(np.float32)
+        vk = vm != 0
+        vk = vk | ~vk.any(1, keepdims=True)
+        off, cnt, src = _pack(vk)
+        out.update(v_off=off, v_cnt=cnt, v_src=src, v_add=v_dense.ravel()[src], v_rows=int(cnt.sum()), v_dense=v_dense, v_keep=vk)
+    return out
+
+
+# ---- e4m3 stores of kernels that compute in fp32 (attention context, LayerNorm rows): checked against the fp64 reference ----
+def f8_excused(ref, delta):
+    """(excused, lo, hi): where ref lies within delta of an e4m3 rounding boundary (the midpoint of two neighbouring codes) an fp32 kernel may land
+    on either neighbour lo / hi; computed from the reference alone."""
+    from oracle import fp8
+    grid = np.unique(fp8.e4m3_decode(np.arange(256))[np.isfinite(fp8.e4m3_decode(np.arange(256)))])
+    mids = (grid[1:] + grid[:-1]) / 2
+    ref = np.asarray(ref, np.float64)
+    j = np.clip(np.searchsorted(mids, ref), 1, len(mids) - 1)
+    j = np.where(np.abs(ref - mids[j - 1]) <= np.abs(ref - mids[j]), j - 1, j)       # nearest boundary: between grid[j] and grid[j + 1]
+    return np.abs(ref - mids[j]) <= delta, grid[j], grid[j + 1]
+
+
+def f8_store_check(ref, got, delta, cap, what):
+    """ref: fp64 reference, got: the decoded bytes.  The excused share is a CONDITION on the inputs (asserted <= cap before the device output is
+    looked at); every other element must be exactly e4m3_round(ref), an excused one either neighbour of its boundary."""
+    from oracle import fp8
+    ref = np.asarray(ref, np.float64)
+    exc, lo, hi = f8_excused(ref, delta)
+    share = float(exc.mean())
+    print("%s: %.2f %% of %d elements within %.1e of an e4m3 rounding boundary" % (what, 100 * share, ref.size, delta))
+    assert share <= cap, (what, share)
+    got = np.asarray(got, np.float64)
+    want = fp8.e4m3_round(ref)
+    bad = np.where(exc, (got != lo) & (got != hi), got != want)
+    assert not bad.any(), (what, int(bad.sum()), ref[bad][:5], got[bad][:5], want[bad][:5])
+    return share
+
+
 def act_ref(x, act):
     """numpy reference of the GEMM epilogue activations (lib.ACT_*)."""
     import math
