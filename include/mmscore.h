@@ -174,11 +174,11 @@ typedef struct mms_ensemble_batch {
 /* ABI revision of the structs and entry points declared in this header.  It changes whenever a struct gains a field or an entry
  * point changes its signature (r1: 1; r2 added mms_config.fuse_layernorm, mms_zk_batch.label_ids, mms_lxmert_batch.label_ids / x_norm
  * without bumping it; r3: 3, then 4 with mms_config.fuse_attention; r4: 5 -- mms_dbg_gemm takes the engine per call,
- * the process-global mms_set_gemm_variant and the lab engines' hooks left the product library, fuse_layernorm became a mask; r5: 6 -- mms_dbg_qkv_attn and mms_side_lane_flops added; r7: 7 -- mms_decode_feats_b64 added).  A caller built against another revision would make the library read past its structs, so compare
+ * the process-global mms_set_gemm_variant and the lab engines' hooks left the product library, fuse_layernorm became a mask; r5: 6 -- mms_dbg_qkv_attn and mms_side_lane_flops added; r7: 7 -- mms_decode_feats_b64 added; r8: 8 -- mms_rank_workspace_bytes and mms_rank_submission added).  A caller built against another revision would make the library read past its structs, so compare
  * BEFORE the first mms_create:  if (mms_version() != MMS_ABI_VERSION) abort();   (lib.py's load() does) */
-#define MMS_ABI_VERSION 7
+#define MMS_ABI_VERSION 8
 int mms_version(void);
-const char* mms_global_error(void);              /* message of the last failing mms_create / mms_decode_feats_b64 */
+const char* mms_global_error(void);              /* message of the last failing mms_create / mms_decode_feats_b64 / mms_rank_submission */
 
 int mms_create(const mms_config* cfg, mms_handle** out);
 void mms_destroy(mms_handle* h);
@@ -254,6 +254,37 @@ int mms_score_ensemble(mms_handle* zk, mms_handle* lds, mms_handle* lxmert, cons
  *   Returns MMS_ERR_ARG (message in mms_global_error, nothing launched) for B < 0, a NULL pointer with B > 0, or a misaligned chars / feats;
  *   B == 0 launches nothing and returns 0.  Handle-free: it needs no model. */
 int mms_decode_feats_b64(const char* chars, const int64_t* char_off, const int32_t* rows, int64_t B, float* feats, int32_t* bad, void* stream);
+
+/* The last step of the job on the device: the global product-uniqueness filter and the per-query top-5 of code/main.py:64-104 over the merged
+ * scores, given as three parallel device arrays of n rows (query_id, product_id int64; score as fp32 OR fp64 -- exactly one of score_f32 /
+ * score_f64 is non-NULL).  Rows of a query may come in any order, interleaved with other queries; the table's query order is the order of
+ * first appearance.  Every comparison is made in IEEE double on the scores converted to double (-0.0 == +0.0):
+ *   per product, over all rows: best, and second = the 2nd entry of its descending score list (two rows at the maximum: second == best);
+ *   keep_product = (rows of the product < 2) or not (best - second < gap);   survive(row) = keep_product and |score - best| < tie;
+ *   a query with >= 5 survivors gets its 5 best survivors; one with 1..4 survivors the 5 best of ALL its rows (fewer if it has fewer); one
+ *   with none gets no output row.  Inside a row: score descending, equal scores in row order.  Output rows: first the queries with >= 5
+ *   survivors, then those with 1..4, each class in first-appearance order (what ensemble.top5 / ensemble.submission_rows produce).
+ * n <= MMS_RANK_MAX_ROWS; no limit on the rows of one query.  Neither id may be MMS_RANK_RESERVED_ID (the empty mark of the hash tables).
+ *   workspace: device memory, 256-byte aligned, at least mms_rank_workspace_bytes(n) bytes (no content expected, none preserved).
+ *   out_query [max_queries], out_products [max_queries][5] (unused entries -1), out_count [max_queries] (products written per row, 1..5).
+ *   status: device int32 [4]:  [0] output rows written  [1] how many of them are of the >= 5-survivor class (they come first)
+ *                              [2] flags  [3] distinct queries seen
+ *   flags:  bit 0  a (query, product) pair occurs more than once (the table semantics "last score wins, first position stays" are NOT
+ *                  implemented here: use the host form)         bit 1  a non-finite score (NaN, +-inf)
+ *           bit 2  more output rows than max_queries            bit 3  an id equal to MMS_RANK_RESERVED_ID
+ *   With a non-zero flag word out_* are unspecified, but nothing is written outside them or outside the workspace.
+ * Only integer atomics whose result does not depend on arrival order: equal inputs give bit-equal outputs on every run.
+ * The call ONLY ENQUEUES on `stream` (three fills, eight kernels): no allocation, no synchronisation, no device -> host read.
+ * Returns MMS_ERR_ARG (message in mms_global_error, nothing launched) for n < 0 or n > MMS_RANK_MAX_ROWS, a NULL pointer with n > 0 (status: always),
+ * both or neither score pointer, a workspace smaller than mms_rank_workspace_bytes(n) or not 256-byte aligned, max_queries < 0.
+ * n == 0 writes a zero status and returns 0.  Handle-free: it needs no model. */
+#define MMS_RANK_MAX_ROWS (1 << 22)
+#define MMS_RANK_RESERVED_ID (-1LL)
+int64_t mms_rank_workspace_bytes(int64_t n);   /* bytes of device workspace mms_rank_submission needs for n rows; a multiple of 256; -1 for n < 0 or n > MMS_RANK_MAX_ROWS */
+int mms_rank_submission(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int64_t n,
+                        double gap, double tie, void* workspace, int64_t workspace_bytes, int64_t max_queries,
+                        int64_t* out_query /* [max_queries] */, int64_t* out_products /* [max_queries][5], unused entries -1 */,
+                        int32_t* out_count /* [max_queries]: products written per row, 1..5 */, int32_t* status /* [4] */, void* stream);
 
 /* accumulated hipEvent time (ms) and launch count of the GEMM kernels since the last reset;
  * enable = 1 brackets every GEMM launch with events on its stream (bench / roofline only) */

@@ -1765,6 +1765,30 @@ int mms_decode_feats_b64(const char* chars, const int64_t* char_off, const int32
     return 0;
 }
 
+int64_t mms_rank_workspace_bytes(int64_t n) {
+    return n < 0 || n > MMS_RANK_MAX_ROWS ? -1 : (int64_t)rank_workspace_bytes(n);
+}
+
+int mms_rank_submission(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int64_t n, double gap,
+                        double tie, void* workspace, int64_t workspace_bytes, int64_t max_queries, int64_t* out_query, int64_t* out_products,
+                        int32_t* out_count, int32_t* status, void* stream) {
+    if (n < 0 || n > MMS_RANK_MAX_ROWS) { g_err = "mms_rank_submission: n must be in [0, MMS_RANK_MAX_ROWS]"; return MMS_ERR_ARG; }
+    if (max_queries < 0) { g_err = "mms_rank_submission: max_queries must be >= 0"; return MMS_ERR_ARG; }
+    if ((score_f32 != nullptr) == (score_f64 != nullptr)) { g_err = "mms_rank_submission: exactly one of score_f32 / score_f64 must be given"; return MMS_ERR_ARG; }
+    if (!status) { g_err = "mms_rank_submission: null status"; return MMS_ERR_ARG; }
+    if (n > 0) {
+        if (!query_id || !product_id || !workspace || !out_query || !out_products || !out_count) { g_err = "mms_rank_submission: null pointer"; return MMS_ERR_ARG; }
+        if (reinterpret_cast<uintptr_t>(workspace) & 255) { g_err = "mms_rank_submission: workspace must be 256-byte aligned"; return MMS_ERR_ARG; }
+        if (workspace_bytes < (int64_t)rank_workspace_bytes(n)) { g_err = "mms_rank_submission: workspace smaller than mms_rank_workspace_bytes(n)"; return MMS_ERR_ARG; }
+    }
+    // (only enqueues: three fills and eight kernels; no allocation, no synchronisation, nothing read back)
+    launch_rank_submission(query_id, product_id, score_f32, score_f64, (int)n, gap, tie, workspace, (int)std::min<int64_t>(max_queries, INT32_MAX), out_query,
+                           out_products, out_count, status, (hipStream_t)stream);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { g_err = std::string("mms_rank_submission: ") + hipGetErrorString(e); return MMS_ERR_HIP; }
+    return 0;
+}
+
 int mms_create(const mms_config* cfg, mms_handle** out) {
     if (!cfg || !out) { g_err = "null argument"; return MMS_ERR_ARG; }
     *out = nullptr;

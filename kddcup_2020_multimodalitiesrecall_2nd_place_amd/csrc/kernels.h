@@ -271,3 +271,10 @@ void launch_quant_rows_f8(const float* w, unsigned char* out, float* scale, unsi
 
 // featdecode.hip: box features of B records from their gathered base64 text -> feats [B,10,2048] fp32 (mms_decode_feats_b64 checks the arguments)
 void launch_decode_feats_b64(const char* chars, const int64_t* char_off, const int32_t* rows, long long B, float* feats, int32_t* bad, hipStream_t st);
+
+// rank.hip: uniqueness filter + per-query top-5 of the merged scores (mms_rank_submission checks the arguments; n <= MMS_RANK_MAX_ROWS, workspace of
+// rank_workspace_bytes(n) bytes, 256-byte aligned).  Enqueues three fills and eight kernels on st; allocates nothing, waits for nothing.
+long long rank_workspace_bytes(long long n);
+void launch_rank_submission(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int n, double gap,
+                            double tie, void* workspace, int max_queries, int64_t* out_query, int64_t* out_products, int32_t* out_count,
+                            int32_t* status, hipStream_t st);

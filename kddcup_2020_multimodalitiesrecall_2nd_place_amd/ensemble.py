@@ -10,7 +10,9 @@ Restates ``code/main.py:41-104`` of the reference:
 * top-5 per query by merged score; a query left with < 5 survivors falls back to its unfiltered
   merged ranking (:93-104).
 The filter is global over queries, so under query sharding it runs on rank 0 after the score gather.
-Pure host-side dict work (29 k entries), exactly as in the reference.
+Host-side dict work (29 k entries) exactly as in the reference (``uniqueness_filter`` / ``top5``), its array form
+(``submission_rows``, the default), and the same decisions on the GPU (``rank_device`` / ``submission_rows_device``:
+``mms_rank_submission``, csrc/rank.hip) for scores that are already device tensors (``sharding.gather_scores``).
 """
 from __future__ import annotations
 
@@ -127,6 +129,82 @@ def submission_rows(query_id, product_id, score, gap=GAP, tie=TIE):
     for qi in short:
         a, b = seg[int(qi)]
         rows[str(int(uq[qi]))] = [str(int(x)) for x in p[rank[a:b][:5]]]
+    return rows
+
+
+FLAG_REPEATED_PAIR, FLAG_NON_FINITE, FLAG_OVERFLOW, FLAG_RESERVED_ID = 1, 2, 4, 8      # status[2] of mms_rank_submission (include/mmscore.h)
+
+
+def rank_device(query_id, product_id, score, gap=GAP, tie=TIE):
+    """The filter + top-5 of ``submission_rows`` on the GPU (``mms_rank_submission``).  ``query_id`` / ``product_id`` / ``score``: device tensors
+    (used in place when int64 / fp32 or fp64 and contiguous), or numpy arrays / host tensors, copied up once.
+    -> (out_query [m] int64, out_products [m, 5] int64 (-1: unused), out_count [m] int32, status [4] int32), device tensors with
+    m = the row count (always enough room); status = (output rows, rows of the >= 5-survivor class -- they come first --, flags, distinct queries).
+    Only enqueues on the current stream: nothing is read back, nothing waits."""
+    import numpy as np
+    import torch
+
+    from . import lib as _lib
+    dev = next((t.device for t in (score, query_id, product_id) if torch.is_tensor(t) and t.is_cuda), torch.device("cuda", torch.cuda.current_device()))
+
+    def up(x, dtypes):
+        t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+        if t.dtype not in dtypes:
+            t = t.to(dtypes[0])
+        return t.to(dev, non_blocking=True).contiguous().reshape(-1)
+
+    q, p = up(query_id, (torch.int64,)), up(product_id, (torch.int64,))
+    s = up(score, (torch.float64, torch.float32))
+    n = s.shape[0]
+    if q.shape[0] != n or p.shape[0] != n:
+        raise ValueError("rank_device: %d query ids, %d product ids, %d scores" % (q.shape[0], p.shape[0], n))
+    l = _lib.load()
+    ws_bytes = l.mms_rank_workspace_bytes(n)
+    if ws_bytes < 0:
+        raise ValueError("rank_device: %d rows, the device path takes at most MMS_RANK_MAX_ROWS (2^22)" % n)
+    m = n                                                                    # at most one output row per input row
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)             # (the caching allocator returns 512-byte aligned blocks)
+    out_query = torch.empty((m,), dtype=torch.int64, device=dev)
+    out_products = torch.empty((m, 5), dtype=torch.int64, device=dev)
+    out_count = torch.empty((m,), dtype=torch.int32, device=dev)
+    status = torch.empty((4,), dtype=torch.int32, device=dev)
+    ptr = lambda t: t.data_ptr() if t.numel() else None
+    f32 = s.dtype == torch.float32
+    # a non-NULL score pointer even for n == 0 (exactly one of the two must be given); never dereferenced then
+    sp = ptr(s) or status.data_ptr()
+    rc = l.mms_rank_submission(ptr(q), ptr(p), sp if f32 else None, None if f32 else sp, n, float(gap), float(tie), ws.data_ptr(), ws_bytes, m,
+                               ptr(out_query), ptr(out_products), ptr(out_count), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise _lib.MmsError("mms_rank_submission failed (%d): %s" % (rc, l.mms_global_error().decode()))
+    return out_query, out_products, out_count, status
+
+
+def submission_rows_device(query_id, product_id, score, gap=GAP, tie=TIE, info=None):
+    """``submission_rows`` with the filter and the top-5 on the GPU (``rank_device``): the same ``OrderedDict`` in the same order.  One host read
+    carries the status and the first rows (room for a query per 8 input rows, at least 4096; a table with more output rows costs a second read).
+    What the device does not do -- a (query, product) pair that occurs twice, a non-finite score, an id equal to the reserved -1 -- it detects:
+    the rows then come from ``submission_rows`` on the host arrays.  ``info`` (a dict) receives ``{"path": "device" | "host", "flags": int}``."""
+    import torch
+    out_query, out_products, out_count, status = rank_device(query_id, product_id, score, gap, tie)
+    m = out_query.shape[0]
+    g = min(m, max(4096, m // 8))
+    pack = lambda k: torch.cat([status.to(torch.int64), out_query[:k], out_count[:k].to(torch.int64), out_products[:k].reshape(-1)])
+    host = pack(g).cpu().numpy()                                             # the one synchronising read
+    n_out, flags = int(host[0]), int(host[2])
+    if info is not None:
+        info.update(path="host" if flags else "device", flags=flags)
+    if flags:
+        to_np = lambda x: x.detach().cpu().numpy() if torch.is_tensor(x) else x
+        return submission_rows(to_np(query_id), to_np(product_id), to_np(score), gap, tie)
+    if n_out > g:
+        g = n_out
+        host = pack(g).cpu().numpy()
+    qs = host[4:4 + n_out].tolist()
+    cnt = host[4 + g:4 + g + n_out].tolist()
+    prods = host[4 + 2 * g:4 + 2 * g + 5 * n_out].tolist()
+    rows = OrderedDict()
+    for i, qq in enumerate(qs):
+        rows[str(qq)] = [str(x) for x in prods[5 * i:5 * i + cnt[i]]]
     return rows
 
 

@@ -361,3 +361,33 @@ class EnsembleScorer:
             return qid, pid, np.zeros(0, np.float64), tuple(np.zeros(0, np.float32) for _ in range(4))
         mem_all = torch.cat([mem for _, mem in out], 1).cpu().numpy()
         return qid, pid, torch.cat([m for m, _ in out]).double().cpu().numpy(), tuple(mem_all[k] for k in range(4))
+
+    def submission_tsv_native(self, tsv_path, vocab_path, label_table, out_path=None, batch_pairs: int = 16384, threads: int = 0,
+                              feat_decode: str = "host", rank: str = "device"):
+        """TSV file -> submission rows (``{query: [p1..p5]}``, optionally written to ``out_path``): the pass of ``score_tsv_native`` with the merged
+        scores left on the device -- no member scores, no score read-back --, the ids uploaded once, and the uniqueness filter + top-5 on the GPU
+        (``ensemble.submission_rows_device``; ``rank="host"``: ``ensemble.submission_rows`` on the fp64 copy of the scores, what a caller of
+        ``score_tsv_native`` does).  Same rows either way."""
+        from . import ensemble
+        if feat_decode not in ("host", "device"):
+            raise ValueError("feat_decode must be 'host' or 'device', not %r" % (feat_decode,))
+        if rank not in ("host", "device"):
+            raise ValueError("rank must be 'host' or 'device', not %r" % (rank,))
+        with _lease(vocab_path, label_table, threads, ("zk", True, feat_decode), ("zk", False, "host"), ("lxmert", False, "host")) as (nf_zk, nf_s2f, nf_lx):
+
+            def batches():
+                for span in nf_zk.iter_spans(tsv_path, batch_pairs, ramp=1024):
+                    zf = nf_zk.featurize_spans(*span)
+                    feed = ensemble_feed(zf, nf_s2f.featurize_spans(*span, True), nf_lx.featurize_spans(*span))
+                    yield zf["query_id"].copy(), zf["product_id"].copy(), {**feed, **{k: zf[k] for k in FEAT_TEXT_KEYS if k in zf}}
+
+            qid, pid, out, _ = _overlapped_pass(batches(), self.zk.device, "feats", lambda d: self.fused.score_prepared(self.fused.prepare(d))[0])
+        if not out:
+            rows = ensemble.submission_rows(qid, pid, np.zeros(0, np.float64))
+        elif rank == "device":
+            rows = ensemble.submission_rows_device(qid, pid, torch.cat(out).double())
+        else:
+            rows = ensemble.submission_rows(qid, pid, torch.cat(out).double().cpu().numpy())
+        if out_path is not None:
+            ensemble.write_submission(out_path, rows)
+        return rows

@@ -48,7 +48,10 @@ def gather_scores(scores: torch.Tensor, query_id: torch.Tensor = None, product_i
     host synchronisation; without them the sizes are exchanged first (an extra small all-gather and a host read).
 
     ``force_collective``: run the collective even in a world of one rank (where the result is the input) -- the same RCCL calls an 8-GPU job
-    issues, on the one GPU a test box has (tests/test_rccl_world1_gpu.py; ``bench.py`` under a launcher with WORLD_SIZE=1)."""
+    issues, on the one GPU a test box has (tests/test_rccl_world1_gpu.py; ``bench.py`` under a launcher with WORLD_SIZE=1).
+
+    The three results are device tensors: on rank 0 they go straight into ``ensemble.submission_rows_device(query_id, product_id, scores)`` (uniqueness
+    filter + top-5 on the GPU, one read-back of the rows) -- or, copied to the host, into ``ensemble.submission_rows``."""
     if not (dist.is_available() and dist.is_initialized()):
         return scores, query_id, product_id
     if dist.get_world_size(group) == 1 and not force_collective:

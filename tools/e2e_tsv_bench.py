@@ -1,7 +1,9 @@
 """End-to-end TSV -> scores throughput (SURVEY.md section 8(f) row 2 + the hot path): synthetic valid/testB-like TSV file,
 native featurizer threads -> pinned buffers -> H2D on a copy stream -> scorer, all overlapped (pipeline.stream_scores_tsv).
-usage (GPU box): python tools/e2e_tsv_bench.py [records] [model] [decode threads, comma list (0 = library default)] [--feat-decode host|device]
-(--feat-decode device: the features' base64 text is gathered on the host and decoded on the GPU; the H2D bytes per record are printed beside pairs/s)"""
+usage (GPU box): python tools/e2e_tsv_bench.py [records] [model] [decode threads, comma list (0 = library default)] [--feat-decode host|device] [--rank host|device]
+(--feat-decode device: the features' base64 text is gathered on the host and decoded on the GPU; the H2D bytes per record are printed beside pairs/s;
+ --rank, ensemble line only: the uniqueness filter + top-5 by ensemble.submission_rows on the host (default) or on the GPU through
+ EnsembleScorer.submission_tsv_native; a comma list prints one line per mode from the same file)"""
 import os
 import sys
 import time
@@ -19,6 +21,11 @@ feat_decode = "host"
 if "--feat-decode" in sys.argv:
     k_ = sys.argv.index("--feat-decode")
     feat_decode = sys.argv[k_ + 1]
+    del sys.argv[k_:k_ + 2]
+rank_modes = ["host"]
+if "--rank" in sys.argv:
+    k_ = sys.argv.index("--rank")
+    rank_modes = sys.argv[k_ + 1].split(",")
     del sys.argv[k_:k_ + 2]
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 30000
 name = sys.argv[2] if len(sys.argv) > 2 else "zk"
@@ -45,15 +52,22 @@ if name == "ensemble":      # BASELINE.json config 5: TSV -> four score tables -
     from kddcup_2020_multimodalitiesrecall_2nd_place_amd import ensemble as E
     sc = {m: scorers.make_scorer(c, weights.make_weights(c), device=0) for m, c in (("zk", ZkConfig()), ("lds", LdsConfig()), ("lxmert", LxmertConfig()))}
     ens = pipeline.EnsembleScorer(sc["zk"], sc["lds"], sc["lxmert"])
-    for _ in range(3):
-        torch.cuda.synchronize(); t0 = time.time()
-        qid, pid, merged, parts = ens.score_tsv_native(path, VOCAB, TABLE, batch_pairs=16384, feat_decode=feat_decode)
-        t1 = time.time()
-        rows = E.submission_rows(qid, pid, merged)          # uniqueness filter + top-5 (main.py:64-104) on the three arrays
-        E.write_submission("/tmp/e2e_submission.csv", rows)
-        dt = time.time() - t0
-    print("TSV -> 4 score tables -> submission.csv, feat_decode %s: %.0f pairs/s end to end (%d pairs, %d queries; scoring %.2f s, post-process %.2f s)"
-          % (feat_decode, len(merged) / dt, len(merged), len(rows), t1 - t0, dt - (t1 - t0)), flush=True)
+    for rank in rank_modes:
+        for _ in range(3):
+            torch.cuda.synchronize(); t0 = time.time()
+            if rank == "device":                                # merged scores stay on the device; filter + top-5 there (csrc/rank.hip)
+                rows = ens.submission_tsv_native(path, VOCAB, TABLE, out_path="/tmp/e2e_submission.csv", batch_pairs=16384, feat_decode=feat_decode)
+                dt = time.time() - t0
+                note = "%d queries" % len(rows)
+            else:
+                qid, pid, merged, parts = ens.score_tsv_native(path, VOCAB, TABLE, batch_pairs=16384, feat_decode=feat_decode)
+                t1 = time.time()
+                rows = E.submission_rows(qid, pid, merged)      # uniqueness filter + top-5 (main.py:64-104) on the three arrays
+                E.write_submission("/tmp/e2e_submission.csv", rows)
+                dt = time.time() - t0
+                note = "%d queries; scoring %.2f s, post-process %.2f s" % (len(rows), t1 - t0, dt - (t1 - t0))
+        print("TSV -> 4 score tables -> submission.csv, feat_decode %s, rank %s: %.0f pairs/s end to end (%d pairs, %.3f s; %s)"
+              % (feat_decode, rank, n / dt, n, dt, note), flush=True)
     os.remove(path)
     sys.exit(0)
 cfg = {"zk": ZkConfig(), "lds": LdsConfig(), "lxmert": LxmertConfig()}[name]
