@@ -334,7 +334,8 @@ int mms_dbg_gemm_f8(const float* a_f32, int64_t M, int64_t K, const float* w_f32
 /* out = LayerNorm(A W^T + bias + resid) over N = 768 through the GEMM with the fused LayerNorm epilogue (gemm_pp_ln.h) and the
  * LayerNorm kernel queued behind it; *mode_out = 1 when the launch ran fused, 2 when it took the plain two-kernel route */
 int mms_dbg_gemm_ln(const float* a_f32, int64_t M, int64_t K, const float* w_f32_nk, const float* bias, const float* resid_f32,
-                    const float* gamma, const float* beta, int32_t f8, float* c_f32, int32_t* mode_out, void* stream);
+                    const float* gamma, const float* beta, int32_t flags /* bit 0: fp8 operands (no such engine: MMS_ERR_ARG); bit 1: the row panels are walked from
+ * the last one down, as every second big launch of a forward walks them (the ragged panel in the first persistent round) */, float* c_f32, int32_t* mode_out, void* stream);
 /* the small-launch route of the same operation (calls of a few hundred pairs): register-staged tiles with the contraction split `splits`
  * ways into fp32 partials (K % (64 * splits) == 0; 1 = unsplit) + the LayerNorm kernel that sums them and adds bias + residual; splits < 0: |splits|
  * partials from the skinny kernel instead (K slices dealt to workgroups, M <= 512): bit-identical to the tile engine's */
@@ -395,6 +396,11 @@ int mms_dbg_dedup(int32_t kind, const void* ids, const int64_t* mask, int32_t T,
  * written).  The planes and the bytes are zero-filled first */
 int mms_dbg_layernorm_ex(const float* x, const float* gamma, const float* beta, int64_t M, const float* resid_f32, int64_t resid_rows, const int32_t* r_index,
                          int64_t m_live, int32_t flags, float* out_f32, float* out_f8, void* stream);
+/* mms_dbg_gemm (two-pass bf16 planes, no residual) with a device-side live-row count and the head-major output of the QKV projections: m_live >= 0: rows >=
+ * min(M, m_live) are not written, < 0: none.  out_kind 0: c_f32 [M][N]; 1: split planes, joined to fp32 [M][N]; 2: head-major fp32 [N / 64][M][64].
+ * reverse 1: the tiles are walked from the last row tile down, as every second big launch of a forward walks them (the ragged tile first).  c_f32 is zero-filled first */
+int mms_dbg_gemm_ex(const float* a_f32, int64_t M, int64_t K, const float* w_f32_nk, int64_t N, const float* bias, int32_t act, int32_t out_kind,
+                    int32_t engine, int64_t m_live, int32_t reverse, float* c_f32, void* stream);
 /* one conversion launcher on n elements (n % 32 == 0).  kind 0: fp32 -> e4m3 bytes; 1: e4m3 bytes -> fp32; 2: fp32 -> split planes -> fp32 (round trip);
  * 3: fp32 -> split planes -> e4m3 bytes */
 int mms_dbg_convert(int32_t kind, const void* in, void* out, int64_t n, void* stream);

@@ -2369,9 +2369,10 @@ unsigned long long* g_ln_dbg = nullptr;   // lab: device buffer for the per-tile
 int mms_lab_ln_trace(unsigned long long* dev_buf) { g_ln_dbg = dev_buf; return MMS_OK; }
 #endif
 int mms_dbg_gemm_ln(const float* a_f32, int64_t M, int64_t K, const float* w_f32_nk, const float* bias, const float* resid_f32,
-                    const float* gamma, const float* beta, int32_t f8, float* c_f32, int32_t* mode_out, void* stream) {
+                    const float* gamma, const float* beta, int32_t flags, float* c_f32, int32_t* mode_out, void* stream) {
     const int64_t N = H;
-    if (!a_f32 || !w_f32_nk || !resid_f32 || !gamma || !beta || !c_f32 || M <= 0 || K % 128) { g_err = "mms_dbg_gemm_ln: bad argument"; return MMS_ERR_ARG; }
+    const bool f8 = flags & 1, reverse = flags & 2;      // bit 0: fp8 operands (refused below); bit 1: GemmParams::reverse, the last row panel in the FIRST round
+    if (!a_f32 || !w_f32_nk || !resid_f32 || !gamma || !beta || !c_f32 || M <= 0 || K % 128 || (flags & ~3)) { g_err = "mms_dbg_gemm_ln: bad argument"; return MMS_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
     bf16 *ap = nullptr, *wp = nullptr, *rp = nullptr, *cp = nullptr;
     unsigned char *a8 = nullptr, *w8 = nullptr;
@@ -2394,12 +2395,13 @@ int mms_dbg_gemm_ln(const float* a_f32, int64_t M, int64_t K, const float* w_f32
     p.c_hi = cp; p.c_lo = cp + MMS_PLANE_LO; p.ldp = (int)N;
     p.out_kind = OUT_F32; p.c_f32 = t; p.ldc = (int)N;
     p.ln_gamma = gamma; p.ln_beta = beta; p.ln_stats = stats; p.ln_tag = 0x5EED0001u; p.ln_ctl = ctl;
+    p.reverse = reverse;
 #ifdef MMS_LAB
     p.ln_dbg = g_ln_dbg;
 #endif
     if (!launch_gemm_pp_ln(p, 2, st)) { g_err = "mms_dbg_gemm_ln: shape not supported"; return MMS_ERR_ARG; }
     LnResid r;
-    r.hi = rp; r.lo = rp + MMS_PLANE_LO; r.ld = (int)N; r.skip = ctl + 1;
+    r.hi = rp; r.lo = rp + MMS_PLANE_LO; r.ld = (int)N; r.skip = ctl + 1; r.reverse = reverse;
     launch_ln_to_planes(t, (int)N, gamma, beta, cp, cp + MMS_PLANE_LO, (int)N, (int)M, st, nullptr, r);
     launch_planes_to_f32(cp, cp + MMS_PLANE_LO, c_f32, M * N, st);
     int ctl_h[2] = {0, 0};
@@ -2793,6 +2795,44 @@ int mms_dbg_dedup(int32_t kind, const void* ids, const int64_t* mask, int32_t T,
     DBG_TRY(hipMemcpyAsync(count_out, counter, 4, hipMemcpyDeviceToHost, st));
     DBG_TRY(hipStreamSynchronize(st));
     DBG_TRY(hipGetLastError());
+    return MMS_OK;
+}
+
+// mms_dbg_gemm with the two fields of a forward's launches it leaves at their defaults: a device-side live-row count (m_live >= 0: rows >= min(M, m_live)
+// are not written; the output is zero-filled first) and the head-major fp32 layout of the QKV projections (out_kind 2: c_f32 [N / 64][M][64]).
+// out_kind 0: plain fp32 [M][N]; 1: split planes, joined to fp32 [M][N].  reverse: GemmParams::reverse (tiles walked from the last row tile down).
+// Two-pass bf16 planes (precision mode 2), no residual.
+int mms_dbg_gemm_ex(const float* a_f32, int64_t M, int64_t K, const float* w_f32_nk, int64_t N, const float* bias, int32_t act, int32_t out_kind,
+                    int32_t engine, int64_t m_live, int32_t reverse, float* c_f32, void* stream) {
+    if (!a_f32 || !w_f32_nk || !c_f32 || M <= 0 || M > (1 << 24) || N % 128 || K % 64 || engine < 0 || out_kind < 0 || out_kind > 2 || (reverse & ~1) || (out_kind == 2 && N % 64)) {
+        g_err = "mms_dbg_gemm_ex: bad argument"; return MMS_ERR_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    DbgPool pool;
+    bf16* ap = (bf16*)pool.get((size_t)M * K * 4);
+    bf16* wp = (bf16*)pool.get((size_t)N * K * 4);
+    bf16* cp = out_kind == 1 ? (bf16*)pool.get((size_t)M * N * 4) : nullptr;
+    int* live = (int*)pool.get(16);
+    if (!ap || !wp || !live || (out_kind == 1 && !cp)) return dbg_fail("mms_dbg_gemm_ex: hipMalloc");
+    const int host_live = (int)m_live;
+    DBG_TRY(hipMemcpyAsync(live, &host_live, 4, hipMemcpyHostToDevice, st));
+    DBG_TRY(hipMemsetAsync(c_f32, 0, (size_t)M * N * 4, st));
+    if (cp) DBG_TRY(hipMemsetAsync(cp, 0, (size_t)M * N * 4, st));
+    launch_split_f32(a_f32, ap, ap + MMS_PLANE_LO, M * K, st);
+    launch_tile_weights(w_f32_nk, wp, wp + N * K, N, K, st);
+    GemmParams p{};
+    p.a_hi = ap; p.a_lo = ap + MMS_PLANE_LO; p.lda = (int)K; p.amap = RowMap{0, 0, 0}; p.cmap = RowMap{0, 0, 0};
+    p.w = wp; p.w_lo = wp + N * K; p.bias = bias; p.M = (int)M; p.N = (int)N; p.K = (int)K; p.act = act;
+    p.engine = engine;
+    if (m_live >= 0) p.m_dev = live;
+    p.reverse = reverse;      // the tile walk of every second big launch of a forward: the ragged row tile comes FIRST
+    if (out_kind == 1) { p.out_kind = OUT_PLANES; p.c_hi = cp; p.c_lo = cp + MMS_PLANE_LO; p.ldp = (int)N; }
+    else { p.out_kind = OUT_F32; p.c_f32 = c_f32; p.ldc = (int)N; if (out_kind == 2) { p.hm_rows = (int)M; p.hm_col0 = 0; } }
+    const bool taken = launch_gemm(p, 2, st);
+    if (taken && out_kind == 1) launch_planes_to_f32(cp, cp + MMS_PLANE_LO, c_f32, M * N, st);
+    DBG_TRY(hipStreamSynchronize(st));
+    DBG_TRY(hipGetLastError());
+    if (!taken) { g_err = "mms_dbg_gemm_ex: no engine takes this shape"; return MMS_ERR_ARG; }
     return MMS_OK;
 }
 

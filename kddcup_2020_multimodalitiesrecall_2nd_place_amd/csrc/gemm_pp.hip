@@ -94,6 +94,17 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmParams p) {
     constexpr int P = 2 * (NSPLIT + 1);             // LDS-DMA pieces per wave per stage (8 KiB = 128 rows per piece)
     static_assert(NSLOT >= 3 && NSLOT * SLOT <= 160 * 1024 && (D - 1) * P < 64, "ring must fit the LDS and the vmcnt counter");
     constexpr int EPI_BYTES = NW * 16 * (TN + 4) * 4;
+    // Tile boundary of a persistent workgroup (bottom of the tile loop).  NST = the vector-memory operations EVERY epilogue issues per wave on a
+    // tile whose rows are all live, behind the next tile's first two stages: one store per row and column fragment as fp32 / e4m3 (FM * FN), two
+    // per fragment pair as split or h3 planes, the same 32 in the LayerNorm epilogue and its plain fall-back.  (Bias / residual loads and lab
+    // stamps only add to it.)  vmcnt counts loads, stores and LDS-DMA together, in issue order, so with at least NST younger operations
+    // `vmcnt(NST + P)` retires stage 0 of the next tile and leaves the stores draining under its MFMAs.  A LOWER bound is what the count needs:
+    // more operations behind the pieces make the wait stricter, fewer would let it pass before they have landed.  The next tile's bias loads
+    // (PRE_BIAS, top of the tile loop) sit in the same window, behind the stores and ahead of stage 0's new pieces: with a bias the chained
+    // stage-0 wait retires four of the stores as well, and the first tile's `vmcnt(P)` the bias -- stricter, both.
+    constexpr int NST = FM * FN;
+    constexpr bool BOUNDARY_COUNTED = PERSIST && D == 2;
+    static_assert(!BOUNDARY_COUNTED || NST + P <= 63, "the boundary wait must fit the 6-bit vmcnt counter");
     static_assert(NSLOT * SLOT >= EPI_BYTES, "epilogue strip must fit in the ring");
     // DIAG 64 (lab): per-phase barrier stamps of waves 0 and 4 of workgroup 0's first tile, kept in 8 KiB of LDS behind the ring (stores to
     // global memory would sit in vmcnt and disturb the counted LDS-DMA waits) and dumped after the tile: tools/pp_phase.py
@@ -276,7 +287,13 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmParams p) {
         __builtin_amdgcn_s_setprio(0);
     };
 
+    // the counted boundary needs stage 0 of a tile to be an ordinary product stage that prefetches a product stage (K >= 160); else full waits
+    const bool counted_ok = BOUNDARY_COUNTED && nk_main > 2 * D;
+    bool chained = false;      // this tile follows another one of the workgroup across a counted boundary
     // PRE: stage s+2 exists and is issued during this stage; WAITN: outstanding pieces allowed at the phase-4 wait
+    // Stage 0 of a chained tile: the previous tile's stores are younger than stage 1's pieces and older than the pieces this stage issues, so
+    // its wait for stage 1 allows NST more (a scalar branch around the wait: a second instantiation of the stage costs the LayerNorm kernel
+    // its last registers).  From stage 1 on the counts are the usual ones: that wait retires the stores.
     // RES (LNF): a residual stage -- W is the identity, so only the wave column that owns the stage's 32 output columns (stage j of the
     // eight: columns 32 j .. 32 j + 31 = half nh = j & 1 of wave column j >> 1) has anything to add: it runs the two quadrants (A0, B_nh),
     // (A1, B_nh) = 16 + 16 MFMAs; the other waves only keep the ring and the barriers going
@@ -293,6 +310,15 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmParams p) {
         const unsigned char* sb = smem + slot * SLOT;
         const int nslot = slot == 0 ? NSLOT - 1 : slot - 1;     // (slot + D) % NSLOT: the slot stage s-1 just left
         constexpr bool DMA = PRE && !(DIAG & 2), RD = !(DIAG & 4);
+        // the phase-B wait for stage s + 1.  Only a product stage that prefetches a product stage can be stage 0 of a chained tile (counted_ok)
+        constexpr bool CAN_CHAIN = BOUNDARY_COUNTED && PRE && !RES && !decltype(nres_tag)::value && WAITN >= 0;
+        auto wait_next_stage = [&](bool after_boundary) {
+            constexpr int W = WAITN >= 0 && !(DIAG & 2) ? WAITN : 0;
+            if constexpr (CAN_CHAIN) {
+                if (after_boundary) { pp_wait_vmcnt<(CAN_CHAIN && !(DIAG & 2) ? NST + W : 0)>(); return; }
+            }
+            if constexpr (WAITN >= 0) pp_wait_vmcnt<W>();
+        };
         auto bar = [&]() { stamp(); if (DIAG & 1) { __builtin_amdgcn_sched_barrier(0); asm volatile("" ::: "memory"); } else pp_barrier(); stamp(); };
 #if MMS_PP_PHASES == 2
         // TWO phases of 2 x 16 MFMAs per stage (round 3): every barrier hand-over between the wave rows costs ~90 cycles of idle matrix pipe
@@ -333,7 +359,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmParams p) {
 #pragma unroll
             for (int q = PI / 2; q < PI; ++q) issue(q, s + D, nslot);
         }
-        if (WAITN >= 0) pp_wait_vmcnt<(WAITN >= 0 && !(DIAG & 2) ? WAITN : 0)>();
+        wait_next_stage(chained && s == 0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         bar();
         if constexpr (RES) {
@@ -407,6 +433,11 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmParams p) {
         for (int i = 0; i < FM; ++i)
 #pragma unroll
             for (int j = 0; j < FN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // the epilogue's bias values are fetched HERE, under the K loop: behind the next tile's first stages (issued below, ahead of the
+        // epilogue) the wait for them would be a wait for those stages' whole round trip as well -- vector-memory operations complete in order
+        constexpr bool PRE_BIAS = PERSIST && !LNF;      // the LayerNorm kernel has no 16 registers for it (and its epilogue waits on its partners anyway)
+        f32x4 bias4[PRE_BIAS ? FN : 1];
+        if constexpr (PRE_BIAS) pp_load_bias<FN>(p, bn * BN + wn * TN, lane, bias4);
         int slot = 0, s = 0;
         auto run_stages = [&](auto res_tag, auto nres_tag, int s_end) {      // stages [s, s_end) of this kind, every one followed by at least D more
             constexpr int PI = decltype(nres_tag)::value ? NAP : P;
@@ -455,13 +486,20 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmParams p) {
             return;
         }
         // PERSIST: the workgroup's next tile.  Its first two stages go out BEFORE this tile's stores (the epilogue needs no LDS), so
-        // their round trip -- the whole prologue of a fresh workgroup -- runs under the store drain; one full `vmcnt(0)` then covers
-        // both, and neither a workgroup retirement nor a dispatch (~4.6 us) sits between two tiles.
+        // neither a workgroup retirement nor a dispatch (~4.6 us) sits between two tiles, and the pieces are OLDER than the stores: the
+        // boundary below waits for stage 0 alone and the store acknowledgements arrive under the next tile's first MFMAs.
         const int row0 = bm * BM + wm * TM, col0 = bn * BN + wn * TN;
         const int ebm = bm, ebn = bn, evb = LNF ? bm * 3 + bn : vb;      // this tile (setup() below moves bm / bn / vb on to the next one)
         int nvb = vb + vstep;
         while (nvb < nblk && !valid(nvb)) nvb += vstep;
         const bool more = PERSIST && nvb < nblk;
+        if constexpr (PRE_BIAS) {
+            // consumed HERE, on every path, with the queue empty behind the K loop: a load that a wave of dead rows never uses stays pending
+            // in the compiler's books across the tile loop, and it then drains the whole queue (`s_waitcnt vmcnt(0)`) in front of the next
+            // write of those registers -- inside the next tile's first stage, where this tile's stores are meant to be still in flight
+#pragma unroll
+            for (int j = 0; j < FN; ++j) asm volatile("" : "+v"(bias4[j]));
+        }
         if (more) {
             vb = nvb;
             setup(vb);
@@ -474,7 +512,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmParams p) {
             if (ln_decided == 1) pp_epilogue_ln<FM, FN>(p, acc, ebm, ebn, wm, wn, lane, tid, Meff, smem + 2 * SLOT, evb);   // ring slot 2 is idle here
             else pp_epilogue_plain_f32<FM, FN>(p, acc, row0, col0, lane, Meff);   // the LayerNorm kernel behind this launch finishes the job
         } else
-        pp_epilogue<ACT, FM, FN>(p, acc, row0, col0, lane, Meff);
+        pp_epilogue<ACT, FM, FN, false, false, PRE_BIAS>(p, acc, row0, col0, lane, Meff, PRE_BIAS ? reinterpret_cast<f32x4(*)[FN]>(&bias4) : nullptr);
         if ((DIAG & 64) && stamping && p.flop_counter) {
             unsigned long long* out = p.flop_counter + (tid >> 8) * 512;
             for (int i = 0; i < 512; ++i) out[i] = i < stamp_i ? reinterpret_cast<unsigned long long*>(smem + NSLOT * SLOT)[(tid >> 8) * 512 + i] : 0ull;
@@ -486,7 +524,11 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(const GemmParams p) {
             t[0] = tr0; t[1] = tr1; t[2] = tr2; t[3] = wall_clock64(); t[4] = ((unsigned long long)bm << 32) | (unsigned)bn;
         }
         if (!more) break;
-        pp_wait_vmcnt<0>();
+        // Counted only where the wave issued every store of the tile (all of its rows live: wave-uniform); a wave of a ragged tile drains.
+        // Either way the wave's own stage-0 pieces have landed before the barrier.
+        if (counted_ok && row0 + TM <= Meff) pp_wait_vmcnt<BOUNDARY_COUNTED ? NST + P : 0>();
+        else pp_wait_vmcnt<0>();
+        chained = counted_ok;
         pp_barrier();
         if (wave >= NW / 2) pp_barrier();     // stagger again
     }

@@ -32,13 +32,28 @@ __device__ __forceinline__ void pp_store_plane_pair(bf16* lane_row, int j, bf16x
 // top of every strip keeps the compiler from copying all 128 of them into arch VGPRs before the first strip (it has only 128 of those)
 // SCALED: the accumulators are in units of a per-column power-of-two scale (p.col_scale: the h3 / fp8 engines of gemm_mx.hip); the bf16
 // engines pass false so that no registers are set aside for it
-template <int ACT, int FM, int FN, bool AGPR_ACC = false, bool SCALED = false>
-__device__ __forceinline__ void pp_epilogue(const GemmParams& p, f32x4 (&acc)[FM][FN], int row0, int col0, int lane, int Meff) {
+// The lane's bias values of the wave's FN column fragments.  The persistent kernel of gemm_pp.hip fetches them at the top of a tile and hands
+// them to pp_epilogue (PRE_BIAS): it issues the next tile's first LDS-DMA stages ahead of the epilogue, and loaded behind those the wait for
+// the bias would be a wait for the stages' whole round trip as well (vector-memory operations complete in issue order).
+template <int FN>
+__device__ __forceinline__ void pp_load_bias(const GemmParams& p, int col0, int lane, f32x4 (&bias4)[FN]) {
+    const int col = col0 + (lane >> 4) * 4;
+#pragma unroll
+    for (int j = 0; j < FN; ++j) bias4[j] = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + col + 16 * j) : f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+template <int ACT, int FM, int FN, bool AGPR_ACC = false, bool SCALED = false, bool PRE_BIAS = false>
+__device__ __forceinline__ void pp_epilogue(const GemmParams& p, f32x4 (&acc)[FM][FN], int row0, int col0, int lane, int Meff, f32x4 (*pre_bias)[FN] = nullptr) {
     const int mrow = lane & 15, nq = lane >> 4;
     const int col = col0 + nq * 4;                       // + 16 j
     f32x4 bias4[FN];
+    if constexpr (PRE_BIAS) {
+#pragma unroll
+        for (int j = 0; j < FN; ++j) bias4[j] = (*pre_bias)[j];
+    } else {
 #pragma unroll
     for (int j = 0; j < FN; ++j) bias4[j] = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + col + 16 * j) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
     // fp8 / h3 weights: the accumulator is in units of the weight row's power-of-two quantisation scale.  Applied strip by strip (not to
     // all accumulators up front): gemm_mx.hip keeps its accumulators in the AGPR half of the register file and only one strip of them
     // should be in arch VGPRs at a time

@@ -170,6 +170,11 @@ __device__ __forceinline__ void pp_epilogue_ln(const GemmParams& p, f32x4 (&acc)
             g4[jj] = *reinterpret_cast<const f32x4*>(p.ln_gamma + col + 16 * (j + jj));
             b4[jj] = *reinterpret_cast<const f32x4*>(p.ln_beta + col + 16 * (j + jj));
         }
+        // consumed HERE, once: every row below is skipped by the lanes past the live count, so the compiler cannot tell in one row's block
+        // that an earlier one has already waited for these loads and repeats the wait in all eight -- `s_waitcnt vmcnt(1)` / `(0)` behind the
+        // previous row's stores, i.e. one full store acknowledgement per row
+#pragma unroll
+        for (int jj = 0; jj < 2; ++jj) asm volatile("" : "+v"(g4[jj]), "+v"(b4[jj]));
 #pragma unroll
         for (int i = 0; i < FM; ++i) {
             const int row = row0 + 16 * i + mrow;

@@ -104,13 +104,8 @@ __device__ __forceinline__ void row_add_planes(Row& x, const bf16* hi, const bf1
 // out = LN(in (+ residual row)).  The residual add sits here rather than in the GEMM epilogue: this kernel streams whole
 // rows at full HBM rate, the epilogue's per-strip residual reads were a latency chain (profiles/r01c_gemm_variants.txt).
 // All of a row's reads precede its writes, so out may alias the residual planes row for row (ffn_block: x -> x).
-__global__ __launch_bounds__(256) void k_ln_to_planes(const float* in, int ld, const float* gamma,
-                                                      const float* beta, bf16* o_hi, bf16* o_lo, int ldo, int M,
-                                                      const int* m_dev, LnResid res) {
-    int row = wave_row();
-    if (res.skip && *res.skip == 1) return;       // the producing GEMM ran its fused LayerNorm epilogue
-    const int lim = m_dev ? min(M, *m_dev) : M;
-    if (row >= lim) return;
+__device__ __forceinline__ void ln_row_to_planes(int row, int lim, const float* in, int ld, const float* gamma, const float* beta, bf16* o_hi, bf16* o_lo,
+                                                 int ldo, const LnResid& res) {
     if (res.reverse) row = lim - 1 - row;
     Row x;
     row_load(x, in + (long long)row * ld);
@@ -126,9 +121,31 @@ __global__ __launch_bounds__(256) void k_ln_to_planes(const float* in, int ld, c
     row_store_planes(x, plane_ptr(o_hi, (long long)row * ldo), plane_ptr(o_lo, (long long)row * ldo));
     if (res.o_f8) row_store_f8(x, res.o_f8 + (long long)row * ldo);
 }
+// STRIDED = false: one wavefront per row.  STRIDED = true (the launches that carry res.skip, i.e. the fall-back queued behind a GEMM with the
+// fused LayerNorm epilogue): a grid of a few workgroups per CU whose wavefronts stride over the rows -- the launch that finds *skip == 1
+// retires a few thousand waves instead of one workgroup per four rows (113 680 of them at 454 720 rows: 50 us of dispatch for nothing).
+// Rows are independent and every row runs ln_row_to_planes either way: the two forms write the same bits.
+template <bool STRIDED>
+__global__ __launch_bounds__(256) void k_ln_to_planes(const float* in, int ld, const float* gamma,
+                                                      const float* beta, bf16* o_hi, bf16* o_lo, int ldo, int M,
+                                                      const int* m_dev, LnResid res) {
+    if (res.skip && *res.skip == 1) return;       // the producing GEMM ran its fused LayerNorm epilogue
+    const int lim = m_dev ? min(M, *m_dev) : M;
+    if constexpr (STRIDED) {
+        for (int row = wave_row(); row < lim; row += (int)gridDim.x * ROWS_PER_BLOCK) ln_row_to_planes(row, lim, in, ld, gamma, beta, o_hi, o_lo, ldo, res);
+    } else {
+        const int row = wave_row();
+        if (row < lim) ln_row_to_planes(row, lim, in, ld, gamma, beta, o_hi, o_lo, ldo, res);
+    }
+}
+#define LN_SKIP_BLOCKS_PER_CU 8      // 32 wavefronts per CU: the kernel's full occupancy
 void launch_ln_to_planes(const float* in, int ld, const float* gamma, const float* beta, bf16* o_hi,
                          bf16* o_lo, int ldo, int M, hipStream_t st, const int* m_dev, LnResid res) {
-    if (M > 0) hipLaunchKernelGGL(k_ln_to_planes, row_grid(M), dim3(256), 0, st, in, ld, gamma, beta, o_hi, o_lo, ldo, M, m_dev, res);
+    if (M <= 0) return;
+    const dim3 grid = row_grid(M);
+    const unsigned bound = (unsigned)device_cu_count() * LN_SKIP_BLOCKS_PER_CU;
+    if (res.skip && grid.x > bound) hipLaunchKernelGGL(k_ln_to_planes<true>, dim3(bound), dim3(256), 0, st, in, ld, gamma, beta, o_hi, o_lo, ldo, M, m_dev, res);
+    else hipLaunchKernelGGL(k_ln_to_planes<false>, grid, dim3(256), 0, st, in, ld, gamma, beta, o_hi, o_lo, ldo, M, m_dev, res);
 }
 
 // Reduce + epilogue of a split-K GEMM launch whose consumer is NOT a LayerNorm (QKV, FFN-up at tiny M: api.hip gemm()): out = act(sum of the

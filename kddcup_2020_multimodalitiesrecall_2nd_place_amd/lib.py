@@ -68,7 +68,7 @@ EXPORTS = ("mms_version", "mms_global_error", "mms_create", "mms_destroy", "mms_
            "mms_finalize", "mms_score_zk", "mms_score_lds", "mms_score_lxmert", "mms_score_ensemble", "mms_gemm_timing", "mms_gemm_timing_class",
            "mms_debug_read_x", "mms_dbg_gemm", "mms_dbg_gemm_f8", "mms_dbg_gemm_ln", "mms_dbg_proj_ln_splitk", "mms_dbg_attention", "mms_dbg_qkv_attn", "mms_dbg_layernorm",
            "mms_dbg_gemm_bench", "mms_dbg_counter", "mms_fused_timing", "mms_side_lane_flops", "mms_decode_feats_b64",
-           "mms_dbg_attention_ex", "mms_dbg_pack_plan", "mms_dbg_dedup", "mms_dbg_layernorm_ex", "mms_dbg_convert", "mms_rank_workspace_bytes", "mms_rank_submission")
+           "mms_dbg_attention_ex", "mms_dbg_pack_plan", "mms_dbg_dedup", "mms_dbg_layernorm_ex", "mms_dbg_gemm_ex", "mms_dbg_convert", "mms_rank_workspace_bytes", "mms_rank_submission")
 LAB_EXPORTS = ("mms_dbg_gemm_mx", "mms_lab_ln_trace")      # libmmscore_lab.so only
 
 _lib = None
@@ -123,6 +123,7 @@ def load(path=None):
     lib.mms_dbg_pack_plan.argtypes = [i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mms_dbg_dedup.argtypes = [i32, vp, vp, i32, i64, C.POINTER(i32), vp, vp, vp, vp, vp]
     lib.mms_dbg_layernorm_ex.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, i32, vp, vp, vp]
+    lib.mms_dbg_gemm_ex.argtypes = [vp, i64, i64, vp, i64, vp, i32, i32, i32, i64, i32, vp, vp]
     lib.mms_dbg_convert.argtypes = [i32, vp, vp, i64, vp]
     lib.mms_dbg_counter.argtypes = [vp, i32]
     lib.mms_fused_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(C.c_double)]
