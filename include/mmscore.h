@@ -174,11 +174,11 @@ typedef struct mms_ensemble_batch {
 /* ABI revision of the structs and entry points declared in this header.  It changes whenever a struct gains a field or an entry
  * point changes its signature (r1: 1; r2 added mms_config.fuse_layernorm, mms_zk_batch.label_ids, mms_lxmert_batch.label_ids / x_norm
  * without bumping it; r3: 3, then 4 with mms_config.fuse_attention; r4: 5 -- mms_dbg_gemm takes the engine per call,
- * the process-global mms_set_gemm_variant and the lab engines' hooks left the product library, fuse_layernorm became a mask; r5: 6 -- mms_dbg_qkv_attn and mms_side_lane_flops added; r7: 7 -- mms_decode_feats_b64 added; r8: 8 -- mms_rank_workspace_bytes and mms_rank_submission added).  A caller built against another revision would make the library read past its structs, so compare
+ * the process-global mms_set_gemm_variant and the lab engines' hooks left the product library, fuse_layernorm became a mask; r5: 6 -- mms_dbg_qkv_attn and mms_side_lane_flops added; r7: 7 -- mms_decode_feats_b64 added; r8: 8 -- mms_rank_workspace_bytes and mms_rank_submission added; r9: 9 -- mms_ndcg_workspace_bytes, mms_key_relevance and mms_ndcg_at_k added).  A caller built against another revision would make the library read past its structs, so compare
  * BEFORE the first mms_create:  if (mms_version() != MMS_ABI_VERSION) abort();   (lib.py's load() does) */
-#define MMS_ABI_VERSION 8
+#define MMS_ABI_VERSION 9
 int mms_version(void);
-const char* mms_global_error(void);              /* message of the last failing mms_create / mms_decode_feats_b64 / mms_rank_submission */
+const char* mms_global_error(void);              /* message of the last failing mms_create / mms_decode_feats_b64 / mms_rank_submission / mms_key_relevance / mms_ndcg_at_k */
 
 int mms_create(const mms_config* cfg, mms_handle** out);
 void mms_destroy(mms_handle* h);
@@ -285,6 +285,53 @@ int mms_rank_submission(const int64_t* query_id, const int64_t* product_id, cons
                         double gap, double tie, void* workspace, int64_t workspace_bytes, int64_t max_queries,
                         int64_t* out_query /* [max_queries] */, int64_t* out_products /* [max_queries][5], unused entries -1 */,
                         int32_t* out_count /* [max_queries]: products written per row, 1..5 */, int32_t* status /* [4] */, void* stream);
+
+/* The valid half of the job on the device: the relevance labels and the nDCG@k decisions of the reference's evaluation (code/imagebert_lds/src/
+ * evaluation.py:4-38; ndcg.ndcg_from_arrays) against an answer key given in CSR form as three device arrays: key_query [n_key_queries] int64,
+ * key_off [n_key_queries + 1] int64 with key_off[0] = 0 and key_off[n_key_queries] = n_key_products, key_product [n_key_products] int64 (key
+ * query i's truth list is key_product[key_off[i] .. key_off[i + 1]); it may be empty, and a product that is repeated in it counts once).
+ * The rows are three parallel device arrays of n entries (query_id, product_id int64; score as fp32 OR fp64 -- exactly one of score_f32 /
+ * score_f64 is non-NULL); rows of a query may come in any order, interleaved with other queries.  Rows whose query is not in the key are
+ * ignored; a (query, product) row that occurs twice counts each time.  No id may be MMS_RANK_RESERVED_ID.
+ *   mms_key_relevance: labels_out[r] = 1 when row r's product is in the truth list of row r's query, else 0 (also for a query outside the
+ *   key) -- the ground-truth label the reference feeds on valid (load_data_v4.py:259-263).
+ *   mms_ndcg_at_k, per key query i: its rows ranked by score descending, equal scores in row order (compared in IEEE double on the scores
+ *   converted to double, -0.0 == +0.0: Python's stable sorted(..., reverse=True));
+ *     mask = bit j set when the j-th ranked row is relevant (j < k);   ideal = min(distinct products of the truth list, k);
+ *     out_code[i] = mask | ideal << 8, or -1 for a key query without rows;   out_topk[i][j] (optional) = the j-th ranked product, -1 past the
+ *     query's rows;   hist[ideal << k | mask] += 1 over the key queries that have rows -- (k + 1) << k int64 bins, zeroed by the call.
+ *   The metric is host arithmetic on these integers: the per-query nDCG is a function of the code alone, ndcg.ndcg_from_codes sums it in key
+ *   order like the host form (bit-identical to it), ndcg.ndcg_from_hist sums bin count x value -- the histogram path differs from the
+ *   sequential sum by summation order only.  Histograms of disjoint query shards add up to the whole table's, exactly.
+ *   allow_missing != 0: key queries without rows are skipped (code -1, no histogram entry) -- what a rank's shard of the rows needs.
+ *   workspace: device memory, 256-byte aligned, at least mms_ndcg_workspace_bytes(n, n_key_queries, n_key_products) bytes (no content
+ *   expected, none preserved).  k in 1..MMS_NDCG_MAX_K.
+ *   status: device int32 [4]:  [0] key queries evaluated (those with rows)   [1] rows that belong to a key query
+ *                              [2] flags                                     [3] key queries without rows
+ *   flags:  bit 0  a key query has no rows while allow_missing == 0 (the host form raises KeyError there; mms_key_relevance never sets it)
+ *           bit 1  a non-finite score (NaN, +-inf)        bit 2  a key query occurs more than once in key_query
+ *           bit 3  an id (row or key) equal to MMS_RANK_RESERVED_ID
+ *   With a non-zero flag word the outputs are unspecified, but nothing is written outside them or outside the workspace.
+ * Only integer atomics whose result does not depend on arrival order: equal inputs give bit-equal outputs on every run.  No kernel waits
+ * on another workgroup.  Both calls ONLY ENQUEUE on `stream` (fills and five / eight kernels): no allocation, no synchronisation, no
+ * device -> host read.  Both are handle-free: they need no model.
+ * Return MMS_ERR_ARG (message in mms_global_error naming the function, nothing launched) for a negative count or one over its cap
+ * (n, n_key_products <= MMS_NDCG_MAX_ROWS, n_key_queries <= MMS_NDCG_MAX_KEY_QUERIES), k outside 1..MMS_NDCG_MAX_K, a NULL pointer whose count is
+ * non-zero (status and hist: always; out_topk may be NULL), key products without key queries, both or neither score pointer, a workspace that is
+ * too small or not 256-byte aligned (needed when n_key_queries > 0).
+ * n == 0 writes a zero histogram, status [0, 0, flags, n_key_queries] (bit 0 unless allow_missing) and every code -1; n_key_queries == 0 writes a
+ * zero histogram and status (and zero labels). */
+#define MMS_NDCG_MAX_ROWS (1 << 22)          /* also the cap on n_key_products */
+#define MMS_NDCG_MAX_KEY_QUERIES (1 << 20)
+#define MMS_NDCG_MAX_K 8
+int64_t mms_ndcg_workspace_bytes(int64_t n, int64_t n_key_queries, int64_t n_key_products);   /* a multiple of 256; -1 outside the caps */
+int mms_key_relevance(const int64_t* query_id, const int64_t* product_id, int64_t n, const int64_t* key_query, const int64_t* key_off,
+                      const int64_t* key_product, int64_t n_key_queries, int64_t n_key_products, void* workspace, int64_t workspace_bytes,
+                      int64_t* labels_out /* [n] 0 / 1 */, int32_t* status /* [4] */, void* stream);
+int mms_ndcg_at_k(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int64_t n,
+                  const int64_t* key_query, const int64_t* key_off, const int64_t* key_product, int64_t n_key_queries, int64_t n_key_products,
+                  int32_t k, int32_t allow_missing, void* workspace, int64_t workspace_bytes, int32_t* out_code /* [n_key_queries] */,
+                  int64_t* out_topk /* [n_key_queries][k] or NULL */, int64_t* hist /* [(k + 1) << k] */, int32_t* status /* [4] */, void* stream);
 
 /* accumulated hipEvent time (ms) and launch count of the GEMM kernels since the last reset;
  * enable = 1 brackets every GEMM launch with events on its stream (bench / roofline only) */

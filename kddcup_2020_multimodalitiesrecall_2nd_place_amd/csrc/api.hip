@@ -1789,6 +1789,63 @@ int mms_rank_submission(const int64_t* query_id, const int64_t* product_id, cons
     return 0;
 }
 
+int64_t mms_ndcg_workspace_bytes(int64_t n, int64_t n_key_queries, int64_t n_key_products) {
+    if (n < 0 || n > MMS_NDCG_MAX_ROWS || n_key_queries < 0 || n_key_queries > MMS_NDCG_MAX_KEY_QUERIES || n_key_products < 0 || n_key_products > MMS_NDCG_MAX_ROWS)
+        return -1;
+    return (int64_t)ndcg_workspace_bytes(n, n_key_queries, n_key_products);
+}
+
+namespace {
+// the checks the two answer-key entry points share; nullptr: the arguments are fine
+const char* ndcg_args(const int64_t* query_id, const int64_t* product_id, int64_t n, const int64_t* key_query, const int64_t* key_off,
+                      const int64_t* key_product, int64_t Qa, int64_t Tk, const void* workspace, int64_t workspace_bytes, const int32_t* status) {
+    if (n < 0 || n > MMS_NDCG_MAX_ROWS) return "n must be in [0, MMS_NDCG_MAX_ROWS]";
+    if (Qa < 0 || Qa > MMS_NDCG_MAX_KEY_QUERIES) return "n_key_queries must be in [0, MMS_NDCG_MAX_KEY_QUERIES]";
+    if (Tk < 0 || Tk > MMS_NDCG_MAX_ROWS) return "n_key_products must be in [0, MMS_NDCG_MAX_ROWS]";
+    if (!status) return "null status";
+    if (n > 0 && (!query_id || !product_id)) return "null pointer";
+    if (Qa > 0 && (!key_query || !key_off)) return "null pointer";
+    if (Tk > 0 && (!key_product || Qa == 0)) return Qa == 0 ? "key products without key queries" : "null pointer";
+    if (Qa > 0) {
+        if (!workspace) return "null pointer";
+        if (reinterpret_cast<uintptr_t>(workspace) & 255) return "workspace must be 256-byte aligned";
+        if (workspace_bytes < (int64_t)ndcg_workspace_bytes(n, Qa, Tk)) return "workspace smaller than mms_ndcg_workspace_bytes(n, n_key_queries, n_key_products)";
+    }
+    return nullptr;
+}
+}  // namespace
+
+int mms_key_relevance(const int64_t* query_id, const int64_t* product_id, int64_t n, const int64_t* key_query, const int64_t* key_off,
+                      const int64_t* key_product, int64_t n_key_queries, int64_t n_key_products, void* workspace, int64_t workspace_bytes,
+                      int64_t* labels_out, int32_t* status, void* stream) {
+    const char* bad = ndcg_args(query_id, product_id, n, key_query, key_off, key_product, n_key_queries, n_key_products, workspace, workspace_bytes, status);
+    if (!bad && n > 0 && !labels_out) bad = "null pointer";
+    if (bad) { g_err = std::string("mms_key_relevance: ") + bad; return MMS_ERR_ARG; }
+    // (only enqueues: fills and five kernels; no allocation, no synchronisation, nothing read back)
+    launch_ndcg(query_id, product_id, nullptr, nullptr, (int)n, key_query, key_off, key_product, (int)n_key_queries, (int)n_key_products, 1, 1, workspace,
+                labels_out, nullptr, nullptr, nullptr, status, (hipStream_t)stream);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { g_err = std::string("mms_key_relevance: ") + hipGetErrorString(e); return MMS_ERR_HIP; }
+    return 0;
+}
+
+int mms_ndcg_at_k(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int64_t n,
+                  const int64_t* key_query, const int64_t* key_off, const int64_t* key_product, int64_t n_key_queries, int64_t n_key_products, int32_t k,
+                  int32_t allow_missing, void* workspace, int64_t workspace_bytes, int32_t* out_code, int64_t* out_topk, int64_t* hist, int32_t* status,
+                  void* stream) {
+    const char* bad = ndcg_args(query_id, product_id, n, key_query, key_off, key_product, n_key_queries, n_key_products, workspace, workspace_bytes, status);
+    if (!bad && (k < 1 || k > MMS_NDCG_MAX_K)) bad = "k must be in [1, MMS_NDCG_MAX_K]";
+    if (!bad && (score_f32 != nullptr) == (score_f64 != nullptr)) bad = "exactly one of score_f32 / score_f64 must be given";
+    if (!bad && (!hist || (n_key_queries > 0 && !out_code))) bad = "null pointer";
+    if (bad) { g_err = std::string("mms_ndcg_at_k: ") + bad; return MMS_ERR_ARG; }
+    // (only enqueues: four fills and eight kernels; no allocation, no synchronisation, nothing read back)
+    launch_ndcg(query_id, product_id, score_f32, score_f64, (int)n, key_query, key_off, key_product, (int)n_key_queries, (int)n_key_products, k,
+                allow_missing != 0, workspace, nullptr, out_code, out_topk, hist, status, (hipStream_t)stream);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { g_err = std::string("mms_ndcg_at_k: ") + hipGetErrorString(e); return MMS_ERR_HIP; }
+    return 0;
+}
+
 int mms_create(const mms_config* cfg, mms_handle** out) {
     if (!cfg || !out) { g_err = "null argument"; return MMS_ERR_ARG; }
     *out = nullptr;

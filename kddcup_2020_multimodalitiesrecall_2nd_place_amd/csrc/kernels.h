@@ -278,3 +278,10 @@ long long rank_workspace_bytes(long long n);
 void launch_rank_submission(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int n, double gap,
                             double tie, void* workspace, int max_queries, int64_t* out_query, int64_t* out_products, int32_t* out_count,
                             int32_t* status, hipStream_t st);
+// ndcg.hip: relevance of every row against the answer key and the nDCG@k codes / histogram (mms_key_relevance / mms_ndcg_at_k check the arguments;
+// workspace of ndcg_workspace_bytes(n, Qa, Tk) bytes, 256-byte aligned).  out_code == nullptr: labels and status only.  Enqueues fills and at most
+// eight kernels on st; allocates nothing, waits for nothing.
+long long ndcg_workspace_bytes(long long n, long long n_key_queries, long long n_key_products);
+void launch_ndcg(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int n, const int64_t* key_query,
+                 const int64_t* key_off, const int64_t* key_product, int Qa, int Tk, int k, int allow_missing, void* workspace, int64_t* labels_out,
+                 int32_t* out_code, int64_t* out_topk, int64_t* hist, int32_t* status, hipStream_t st);

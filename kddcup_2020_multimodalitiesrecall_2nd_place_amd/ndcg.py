@@ -39,3 +39,222 @@ def ndcg_from_arrays(query_id, product_id, score, rank_label: dict, k: int = 5) 
     for q, p, s in zip(query_id, product_id, score):
         pred.setdefault(str(int(q)), []).append((str(int(p)), float(s)))
     return evaluate_ndcg(pred, rank_label, k)
+
+
+# ---- integer form: per key query a CODE, the metric a function of the codes (what mms_ndcg_at_k computes on the device, csrc/ndcg.hip) ----
+# code = mask | ideal << 8: bit j of mask is set when the j-th ranked row of the query is relevant (j < k), ideal = min(len(set(truth)), k);
+# -1 for a key query without rows.  hist[ideal << k | mask] counts the key queries per code.
+FLAG_MISSING_QUERY, FLAG_NON_FINITE, FLAG_REPEATED_KEY, FLAG_RESERVED_ID = 1, 2, 4, 8      # status[2] of mms_ndcg_at_k (include/mmscore.h)
+MAX_K = 8                                                                                  # MMS_NDCG_MAX_K
+
+
+def _key_lists(rank_label: dict):
+    """-> (key query ids, truth lists of ints) in the key's own order."""
+    return [int(q) for q in rank_label], [[int(p) for p in truth] for truth in rank_label.values()]
+
+
+def ndcg_codes(query_id, product_id, score, rank_label: dict, k: int = 5, allow_missing: bool = False, return_topk: bool = False):
+    """The numpy host form of the device codes: per key query a stable argsort on ``-float64(score)`` of its rows (rows in any order,
+    interleaved with other queries) and ``set(truth)``.  -> int32 [len(rank_label)] in key order (and, with ``return_topk``, the ranked
+    product ids int64 [len, k], -1 past a query's rows).  A key query without rows raises ``KeyError`` like ``ndcg_from_arrays``
+    unless ``allow_missing`` (its code is -1 then)."""
+    if not 1 <= k <= MAX_K:
+        raise ValueError("k must be in 1..%d" % MAX_K)
+    q = np.asarray(query_id).astype(np.int64).reshape(-1)
+    p = np.asarray(product_id).astype(np.int64).reshape(-1)
+    s = np.asarray(score).astype(np.float64).reshape(-1)
+    keys, truths = _key_lists(rank_label)
+    by_q = np.argsort(q, kind="stable")                  # rows of a query stay in row order
+    qs = q[by_q]
+    codes = np.empty(len(keys), np.int32)
+    topk = np.full((len(keys), k), -1, np.int64)
+    for i, (kq, truth) in enumerate(zip(keys, truths)):
+        rows = by_q[np.searchsorted(qs, kq, "left"):np.searchsorted(qs, kq, "right")]
+        if rows.size == 0:
+            if not allow_missing:
+                raise KeyError(str(kq))
+            codes[i] = -1
+            continue
+        top = rows[np.argsort(-s[rows], kind="stable")[:k]]          # -0.0 and +0.0 compare equal: a tie, kept in row order
+        gt = set(truth)
+        mask = sum(1 << j for j, r in enumerate(top) if int(p[r]) in gt)
+        codes[i] = mask | min(len(gt), k) << 8
+        topk[i, :top.size] = p[top]
+    return (codes, topk) if return_topk else codes
+
+
+def _code_value(code: int, k: int) -> float:
+    """nDCG@k of one key query from its code -- ``get_ndcg`` on the mask's bits: the arithmetic lives in one place."""
+    return get_ndcg([float(code >> j & 1) for j in range(k)], [1.0] * (code >> 8), k)
+
+
+def ndcg_from_codes(codes, k: int = 5) -> float:
+    """Sum of the per-query values in key order, divided by the key length: the sum ``evaluate_ndcg`` makes, term for term (bit-identical).
+    Codes of -1 (key queries without rows, ``allow_missing``) add nothing."""
+    total, memo = 0.0, {}
+    codes = np.asarray(codes).reshape(-1).tolist()
+    for c in codes:
+        if c < 0:
+            continue
+        if c not in memo:
+            memo[c] = _code_value(c, k)
+        total += memo[c]
+    return total / len(codes)
+
+
+def hist_from_codes(codes, k: int = 5):
+    """The device histogram of a code array: int64 [(k + 1) << k], bin ``ideal << k | mask``."""
+    c = np.asarray(codes).reshape(-1).astype(np.int64)
+    c = c[c >= 0]
+    return np.bincount((c >> 8) << k | (c & 0xFF), minlength=(k + 1) << k).astype(np.int64)
+
+
+def ndcg_from_hist(hist, k: int, n_queries: int) -> float:
+    """sum(hist[bin] * value(bin)) / n_queries over the non-empty bins in bin order: the terms of ``ndcg_from_codes`` summed per bin, so the two
+    differ by summation order only.  Histograms add (query shards: ``sharding.reduce_ndcg``); ``n_queries`` is the whole key's length."""
+    h = np.asarray(hist).reshape(-1)
+    if h.shape[0] != (k + 1) << k:
+        raise ValueError("a k = %d histogram has %d bins, not %d" % (k, (k + 1) << k, h.shape[0]))
+    total = 0.0
+    for b in np.flatnonzero(h).tolist():
+        total += int(h[b]) * _code_value((b >> k) << 8 | (b & ((1 << k) - 1)), k)
+    return total / n_queries
+
+
+class AnswerKey:
+    """An answer key on the device in the CSR form of include/mmscore.h: ``key_query`` [Qa], ``key_off`` [Qa + 1], ``key_product`` [Tk] (int64
+    device tensors).  Built once from the ``{query: [products]}`` dict and passed wherever ``rank_label`` is taken, it saves the upload per call."""
+
+    def __init__(self, rank_label: dict, device=None):
+        import torch
+        self.rank_label = rank_label
+        keys, truths = _key_lists(rank_label)
+        off = np.zeros(len(keys) + 1, np.int64)
+        np.cumsum([len(t) for t in truths], out=off[1:])
+        prod = np.array([p for t in truths for p in t], np.int64)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        up = lambda a: torch.from_numpy(a).to(self.device, non_blocking=True)
+        self.key_query, self.key_off, self.key_product = up(np.array(keys, np.int64)), up(off), up(prod)
+        self.n_queries, self.n_products = len(keys), int(prod.shape[0])
+
+
+def _key_on(rank_label, dev):
+    if isinstance(rank_label, AnswerKey):
+        if rank_label.device != dev:
+            raise ValueError("the AnswerKey lives on %s, the rows on %s" % (rank_label.device, dev))
+        return rank_label
+    return AnswerKey(rank_label, dev)
+
+
+def _rows_on_device(arrays, dtypes, what):
+    """The row arrays as flat contiguous device tensors (used in place when they already are), the device they live on."""
+    import torch
+    dev = next((t.device for t in arrays if torch.is_tensor(t) and t.is_cuda), torch.device("cuda", torch.cuda.current_device()))
+    out = []
+    for x, dt in zip(arrays, dtypes):
+        t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
+        if t.dtype not in dt:
+            t = t.to(dt[0])
+        out.append(t.to(dev, non_blocking=True).contiguous().reshape(-1))
+    if len({t.shape[0] for t in out}) != 1:
+        raise ValueError("%s: row arrays of %s entries" % (what, " / ".join(str(t.shape[0]) for t in out)))
+    return out, dev
+
+
+def _workspace(l, n, key, dev, what):
+    import torch
+    ws_bytes = l.mms_ndcg_workspace_bytes(n, key.n_queries, key.n_products)
+    if ws_bytes < 0:
+        raise ValueError("%s: %d rows, %d key queries, %d key products: the device path takes at most 2^22 rows / key products and 2^20 key queries"
+                         % (what, n, key.n_queries, key.n_products))
+    return torch.empty((ws_bytes,), dtype=torch.uint8, device=dev), ws_bytes      # (the caching allocator returns 512-byte aligned blocks)
+
+
+_ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+
+
+def relevance_device(query_id, product_id, rank_label, status_out: list = None):
+    """The ground-truth labels of the rows on the GPU (``mms_key_relevance``): int64 device tensor [n], 1 where the row's product is in its query's
+    truth list.  ``rank_label``: the ``{query: [products]}`` dict or an ``AnswerKey``.  Only enqueues on the current stream; ``status_out`` (a list)
+    receives the device status tensor [4] (rows of key queries in [1], flags in [2]) for a caller that wants to read it later."""
+    import torch
+
+    from . import lib as _lib
+    (q, p), dev = _rows_on_device((query_id, product_id), ((torch.int64,), (torch.int64,)), "relevance_device")
+    key = _key_on(rank_label, dev)
+    n = q.shape[0]
+    l = _lib.load()
+    ws, ws_bytes = _workspace(l, n, key, dev, "relevance_device")
+    labels = torch.empty((n,), dtype=torch.int64, device=dev)
+    status = torch.empty((4,), dtype=torch.int32, device=dev)
+    rc = l.mms_key_relevance(_ptr(q), _ptr(p), n, _ptr(key.key_query), _ptr(key.key_off), _ptr(key.key_product), key.n_queries, key.n_products,
+                             ws.data_ptr(), ws_bytes, _ptr(labels), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise _lib.MmsError("mms_key_relevance failed (%d): %s" % (rc, l.mms_global_error().decode()))
+    if status_out is not None:
+        status_out.append(status)
+    return labels
+
+
+def ndcg_codes_device(query_id, product_id, score, rank_label, k: int = 5, allow_missing: bool = False, want_topk: bool = False):
+    """``mms_ndcg_at_k`` on device tensors (used in place when int64 / fp32 or fp64 and contiguous) or host arrays (copied up once).
+    -> (codes int32 [Qa], topk int64 [Qa, k] or None, hist int64 [(k + 1) << k], status int32 [4]), device tensors.  Only enqueues on the
+    current stream: nothing is read back, nothing waits."""
+    import torch
+
+    from . import lib as _lib
+    if not 1 <= k <= MAX_K:
+        raise ValueError("k must be in 1..%d" % MAX_K)
+    (q, p, s), dev = _rows_on_device((query_id, product_id, score), ((torch.int64,), (torch.int64,), (torch.float64, torch.float32)), "ndcg_device")
+    key = _key_on(rank_label, dev)
+    n = s.shape[0]
+    l = _lib.load()
+    ws, ws_bytes = _workspace(l, n, key, dev, "ndcg_device")
+    codes = torch.empty((key.n_queries,), dtype=torch.int32, device=dev)
+    topk = torch.empty((key.n_queries, k), dtype=torch.int64, device=dev) if want_topk else None
+    hist = torch.empty(((k + 1) << k,), dtype=torch.int64, device=dev)
+    status = torch.empty((4,), dtype=torch.int32, device=dev)
+    f32 = s.dtype == torch.float32
+    sp = _ptr(s) or status.data_ptr()        # a non-NULL score pointer even for n == 0 (exactly one of the two must be given); never dereferenced then
+    rc = l.mms_ndcg_at_k(_ptr(q), _ptr(p), sp if f32 else None, None if f32 else sp, n, _ptr(key.key_query), _ptr(key.key_off), _ptr(key.key_product),
+                         key.n_queries, key.n_products, k, int(bool(allow_missing)), ws.data_ptr(), ws_bytes, _ptr(codes), _ptr(topk), hist.data_ptr(),
+                         status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise _lib.MmsError("mms_ndcg_at_k failed (%d): %s" % (rc, l.mms_global_error().decode()))
+    return codes, topk, hist, status
+
+
+def ndcg_device(query_id, product_id, score, rank_label, k: int = 5, info: dict = None, allow_missing: bool = False, return_hist: bool = False):
+    """``ndcg_from_arrays`` with the ranking on the GPU (``mms_ndcg_at_k``): the same float, bit for bit.  The rows may be device tensors (the
+    scores stay where the scorer left them) or host arrays; ``rank_label`` the ``{query: [products]}`` dict or an ``AnswerKey``.  ONE small host
+    read carries the status and the codes (4 bytes per key query) -- or, with ``return_hist``, the status and the histogram, and the result is
+    ``(hist int64 numpy [(k + 1) << k], key queries evaluated)`` for ``sharding.reduce_ndcg`` / ``ndcg_from_hist``.
+    ``allow_missing``: key queries without rows add nothing (a rank's shard); without it they raise ``KeyError`` like the host form.
+    What the device does not do -- a non-finite score, a repeated key query, an id equal to the reserved -1 -- it detects: the value then
+    comes from the host form on the host arrays.  ``info`` (a dict) receives ``{"path": "device" | "host", "flags": int}``."""
+    import torch
+    label_dict = rank_label.rank_label if isinstance(rank_label, AnswerKey) else rank_label
+    if len(label_dict) == 0:
+        return ndcg_from_arrays([], [], [], label_dict, k)                   # the host form's own error for an empty key
+    codes, _, hist, status = ndcg_codes_device(query_id, product_id, score, rank_label, k, allow_missing)
+    out = hist if return_hist else codes.to(torch.int64)
+    host = torch.cat([status.to(torch.int64), out]).cpu().numpy()            # the one synchronising read
+    flags, body = int(host[2]), host[4:]
+    if info is not None:
+        info.update(path="host" if flags & ~FLAG_MISSING_QUERY else "device", flags=flags)
+    if flags & ~FLAG_MISSING_QUERY:
+        to_np = lambda x: x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+        qh, ph, sh = to_np(query_id), to_np(product_id), to_np(score)
+        if return_hist:
+            c = ndcg_codes(qh, ph, sh, label_dict, k, allow_missing)
+            return hist_from_codes(c, k), int((c >= 0).sum())
+        if allow_missing:
+            return ndcg_from_codes(ndcg_codes(qh, ph, sh, label_dict, k, True), k)
+        return ndcg_from_arrays(qh, ph, sh, label_dict, k)
+    if flags & FLAG_MISSING_QUERY:                                           # only without allow_missing
+        if return_hist:
+            raise KeyError("%d key queries have no rows" % int(host[3]))
+        raise KeyError(str(_key_lists(label_dict)[0][int(np.flatnonzero(body < 0)[0])]))
+    if return_hist:
+        return body.copy(), int(host[0])
+    return ndcg_from_codes(body, k)

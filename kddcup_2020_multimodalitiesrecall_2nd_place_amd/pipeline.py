@@ -250,6 +250,30 @@ def stream_scores_tsv(scorer, tsv_path, vocab_path, label_table, sen2forest: boo
     the scorer's kernels.  Scores are bit-identical to the host mode's; a record whose text is not base64 raises ValueError (naming it) before
     the pass returns.
     """
+    qid, pid, probs, counts = _model_pass(scorer, tsv_path, vocab_path, label_table, sen2forest, batch_pairs, threads, ramp, shard, shard_by, stats,
+                                          feat_decode)
+    score = torch.cat(probs).float().cpu().numpy() if probs else np.zeros(0, np.float32)
+    if shard is not None:
+        return qid, pid, score, counts
+    return qid, pid, score
+
+
+def _answer_labels(key):
+    """-> a hook for the passes below: the batch's ``labels`` feed (zk's AM-softmax margin reads it) becomes the ground-truth 0/1 of the batch's own
+    (query, product) ids against the answer key, computed on the scoring stream in front of the scorer's kernels (``ndcg.relevance_device``) --
+    what the reference feeds on valid (load_data_v4.py:259-263).  A feed without ``labels`` (lds, lxmert) is left as it is."""
+    from . import ndcg
+
+    def hook(d):
+        if "labels" in d:
+            d["labels"] = ndcg.relevance_device(d["_query_id"], d["_product_id"], key)
+        return d
+    return hook
+
+
+def _model_pass(scorer, tsv_path, vocab_path, label_table, sen2forest, batch_pairs, threads, ramp, shard, shard_by, stats, feat_decode, relabel=None):
+    """The overlapped pass of ``stream_scores_tsv`` with the scores left on the device: -> (query_id, product_id, [softmax(logit)[:, 1] per batch],
+    counts).  ``relabel`` (``_answer_labels``): the batch's ids travel to the device with it and the hook rewrites the device feed before scoring."""
     if feat_decode not in ("host", "device"):
         raise ValueError("feat_decode must be 'host' or 'device', not %r" % (feat_decode,))
     if shard is not None and threads <= 0:
@@ -264,15 +288,67 @@ def stream_scores_tsv(scorer, tsv_path, vocab_path, label_table, sen2forest: boo
 
         def batches():
             for b in nf.iter_file(tsv_path, batch_pairs, sen2forest, ramp=ramp, records=records, byte_range=byte_range):
-                yield b.pop("query_id").copy(), b.pop("product_id").copy(), b
+                q, pr = b.pop("query_id").copy(), b.pop("product_id").copy()
+                if relabel is not None:
+                    b = {**b, "_query_id": q, "_product_id": pr}
+                yield q, pr, b
 
-        qid, pid, probs, st = _overlapped_pass(batches(), scorer.device, nf.FEAT_KEY[nf.model], lambda d: score_batch(scorer, d)[1][:, 1])
-        score = torch.cat(probs).float().cpu().numpy() if probs else np.zeros(0, np.float32)
+        score = (lambda d: score_batch(scorer, d)[1][:, 1]) if relabel is None else (lambda d: score_batch(scorer, relabel(d))[1][:, 1])
+        qid, pid, probs, st = _overlapped_pass(batches(), scorer.device, nf.FEAT_KEY[nf.model], score)
         if stats is not None:
             stats.update(st, featurizer={k: v - before.get(k, 0.0) for k, v in nf.stats.items()})
-    if shard is not None:
-        return qid, pid, score, counts
-    return qid, pid, score
+    return qid, pid, probs, counts
+
+
+def _metric(qid, pid, score, rank_label, k, metric, sharded, info):
+    """nDCG@k of a pass: ``metric="device"``: ``ndcg.ndcg_device`` on the device scores (one small read); ``"host"``: ``ndcg.ndcg_from_arrays`` on
+    their copy.  The same value.  ``sharded``: -> (histogram, key queries evaluated) of this rank's rows for ``sharding.reduce_ndcg``."""
+    from . import ndcg
+    if metric == "device":
+        return ndcg.ndcg_device(qid, pid, score, rank_label, k, info=info, allow_missing=sharded, return_hist=sharded)
+    label_dict = rank_label.rank_label if isinstance(rank_label, ndcg.AnswerKey) else rank_label
+    host = score.cpu().numpy()
+    if info is not None:
+        info.update(path="host", flags=0)
+    if sharded:
+        codes = ndcg.ndcg_codes(qid, pid, host, label_dict, k, allow_missing=True)
+        return ndcg.hist_from_codes(codes, k), int((codes >= 0).sum())
+    return ndcg.ndcg_from_arrays(qid, pid, host, label_dict, k)
+
+
+def _check_eval_args(metric, labels):
+    if metric not in ("host", "device"):
+        raise ValueError("metric must be 'host' or 'device', not %r" % (metric,))
+    if labels not in ("answer", "ones"):
+        raise ValueError("labels must be 'answer' or 'ones', not %r" % (labels,))
+
+
+def evaluate_tsv_native(scorer, tsv_path, vocab_path, label_table, rank_label, k: int = 5, metric: str = "device", labels: str = "answer",
+                        sen2forest: bool = False, batch_pairs: int = 32768, threads: int = 0, ramp: int = 1024, shard=None, shard_by: str = "bytes",
+                        stats: dict = None, feat_decode: str = "host", info: dict = None, scores_out: dict = None):
+    """A valid TSV file -> nDCG@k against the answer key ``rank_label`` (``{query: [products]}`` or an ``ndcg.AnswerKey``), the reference's valid
+    protocol: the pass of ``stream_scores_tsv`` (same streaming arguments) with the scores left on the device.
+
+    ``labels="answer"`` (default): the label feed of the model -- zk's AM-softmax margin depends on it -- is the ground truth of each batch's
+    own ids, looked up in the answer key on the GPU (``ndcg.relevance_device``), as the reference feeds it on valid; ``labels="ones"`` keeps the
+    testB convention of ``stream_scores_tsv`` (every label 1).  lds and lxmert read no label: the same scores either way.
+    ``metric="device"``: ranking per key query on the GPU (``ndcg.ndcg_device``), one small host read; ``metric="host"``: ``ndcg.ndcg_from_arrays``
+    on the copied scores.  Both return the same float, bit for bit.
+    ``shard = (rank, world)``: this rank's rows only; the result is ``(histogram, key queries evaluated)`` for ``sharding.reduce_ndcg`` +
+    ``ndcg.ndcg_from_hist`` instead of the float.  ``info`` receives the metric's ``{"path", "flags"}``; ``scores_out`` (a dict) receives
+    ``query_id`` / ``product_id`` (numpy) and ``score`` (device fp32)."""
+    from . import ndcg
+    _check_eval_args(metric, labels)
+    relabel = None
+    if labels == "answer" and scorer.cfg.name == "zk":
+        rank_label = rank_label if isinstance(rank_label, ndcg.AnswerKey) else ndcg.AnswerKey(rank_label, scorer.device)
+        relabel = _answer_labels(rank_label)
+    qid, pid, probs, _ = _model_pass(scorer, tsv_path, vocab_path, label_table, sen2forest, batch_pairs, threads, ramp, shard, shard_by, stats,
+                                     feat_decode, relabel)
+    score = torch.cat(probs).float() if probs else torch.zeros(0, dtype=torch.float32, device=scorer.device)
+    if scores_out is not None:
+        scores_out.update(query_id=qid, product_id=pid, score=score)
+    return _metric(qid, pid, score, rank_label, k, metric, shard is not None, info)
 
 
 def predict_tsv_native(scorer, tsv_path, vocab_path, label_table, out_path, sen2forest: bool = False, batch_pairs: int = 32768,
@@ -339,12 +415,9 @@ class EnsembleScorer:
         pid = np.array([r.product_id for r in rec], np.int64)
         return qid, pid, cat(merged, np.float64), tuple(cat(x, np.float32) for x in parts)
 
-    def score_tsv_native(self, tsv_path, vocab_path, label_table, batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host"):
-        """``score_lines`` on a TSV file through libmmfeat, decode and scoring overlapped: a producer thread decodes span batch i+1
-        three times (zk flavour, zk with the sen2forest rewrite, lxmert flavour; ctypes releases the GIL, each featurizer rotates
-        three pinned buffer sets) while the main thread copies batch i to the device and runs the ONE fused call on it.
-        ``feat_decode="device"``: the zk-flavour pass gathers the features' base64 text and the GPU decodes it on the scoring stream in front of
-        the fused call (``stream_scores_tsv``); same scores, a bad record raises ValueError before the pass returns."""
+    def _tsv_pass(self, tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members, relabel=None):
+        """The overlapped pass of the file-fed ensemble drivers with the outputs left on the device: -> (query_id, product_id, per batch: (merged,
+        member scores or None without ``members``)).  ``relabel``: see ``_answer_labels``."""
         if feat_decode not in ("host", "device"):
             raise ValueError("feat_decode must be 'host' or 'device', not %r" % (feat_decode,))
         # (kept between calls like stream_scores_tsv's; the fused feed reads the 2048-d features from the first pass only, the other two flavours skip their decode)
@@ -354,9 +427,42 @@ class EnsembleScorer:
                 for span in nf_zk.iter_spans(tsv_path, batch_pairs, ramp=1024):      # (ramp: the first fused call starts after 1024 records)
                     zf = nf_zk.featurize_spans(*span)
                     feed = ensemble_feed(zf, nf_s2f.featurize_spans(*span, True), nf_lx.featurize_spans(*span))
-                    yield zf["query_id"].copy(), zf["product_id"].copy(), {**feed, **{k: zf[k] for k in FEAT_TEXT_KEYS if k in zf}}
+                    q, pr = zf["query_id"].copy(), zf["product_id"].copy()
+                    ids = {} if relabel is None else {"_query_id": q, "_product_id": pr}
+                    yield q, pr, {**feed, **{k: zf[k] for k in FEAT_TEXT_KEYS if k in zf}, **ids}
 
-            qid, pid, out, _ = _overlapped_pass(batches(), self.zk.device, "feats", lambda d: self.fused.score_prepared(self.fused.prepare(d)))
+            def score(d):
+                prep = self.fused.prepare(d if relabel is None else relabel(d))
+                return self.fused.score_prepared(prep) if members else self.fused.score_prepared(prep, False)
+
+            qid, pid, out, _ = _overlapped_pass(batches(), self.zk.device, "feats", score)
+        return qid, pid, out
+
+    def evaluate_tsv_native(self, tsv_path, vocab_path, label_table, rank_label, k: int = 5, metric: str = "device", labels: str = "answer",
+                            batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host", info: dict = None, scores_out: dict = None):
+        """A valid TSV file -> nDCG@k of the merged scores against the answer key (``pipeline.evaluate_tsv_native``, which see, for the ensemble):
+        the pass of ``score_tsv_native`` with the merged scores left on the device, the zk members' label feed from the answer key
+        (``labels="answer"``) or all ones (``labels="ones"``, today's feed), the metric on the GPU (``metric="device"``) or by
+        ``ndcg.ndcg_from_arrays`` on the fp64 copy of the scores (``metric="host"``) -- the same float."""
+        from . import ndcg
+        _check_eval_args(metric, labels)
+        relabel = None
+        if labels == "answer":
+            rank_label = rank_label if isinstance(rank_label, ndcg.AnswerKey) else ndcg.AnswerKey(rank_label, self.zk.device)
+            relabel = _answer_labels(rank_label)
+        qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=False, relabel=relabel)
+        score = torch.cat([m for m, _ in out]).double() if out else torch.zeros(0, dtype=torch.float64, device=self.zk.device)
+        if scores_out is not None:
+            scores_out.update(query_id=qid, product_id=pid, score=score)
+        return _metric(qid, pid, score, rank_label, k, metric, False, info)
+
+    def score_tsv_native(self, tsv_path, vocab_path, label_table, batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host"):
+        """``score_lines`` on a TSV file through libmmfeat, decode and scoring overlapped: a producer thread decodes span batch i+1
+        three times (zk flavour, zk with the sen2forest rewrite, lxmert flavour; ctypes releases the GIL, each featurizer rotates
+        three pinned buffer sets) while the main thread copies batch i to the device and runs the ONE fused call on it.
+        ``feat_decode="device"``: the zk-flavour pass gathers the features' base64 text and the GPU decodes it on the scoring stream in front of
+        the fused call (``stream_scores_tsv``); same scores, a bad record raises ValueError before the pass returns."""
+        qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=True)
         if not out:
             return qid, pid, np.zeros(0, np.float64), tuple(np.zeros(0, np.float32) for _ in range(4))
         mem_all = torch.cat([mem for _, mem in out], 1).cpu().numpy()
@@ -373,15 +479,8 @@ class EnsembleScorer:
             raise ValueError("feat_decode must be 'host' or 'device', not %r" % (feat_decode,))
         if rank not in ("host", "device"):
             raise ValueError("rank must be 'host' or 'device', not %r" % (rank,))
-        with _lease(vocab_path, label_table, threads, ("zk", True, feat_decode), ("zk", False, "host"), ("lxmert", False, "host")) as (nf_zk, nf_s2f, nf_lx):
-
-            def batches():
-                for span in nf_zk.iter_spans(tsv_path, batch_pairs, ramp=1024):
-                    zf = nf_zk.featurize_spans(*span)
-                    feed = ensemble_feed(zf, nf_s2f.featurize_spans(*span, True), nf_lx.featurize_spans(*span))
-                    yield zf["query_id"].copy(), zf["product_id"].copy(), {**feed, **{k: zf[k] for k in FEAT_TEXT_KEYS if k in zf}}
-
-            qid, pid, out, _ = _overlapped_pass(batches(), self.zk.device, "feats", lambda d: self.fused.score_prepared(self.fused.prepare(d))[0])
+        qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=True)
+        out = [m for m, _ in out]
         if not out:
             rows = ensemble.submission_rows(qid, pid, np.zeros(0, np.float64))
         elif rank == "device":

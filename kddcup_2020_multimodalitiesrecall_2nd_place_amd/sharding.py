@@ -86,3 +86,16 @@ def gather_scores(scores: torch.Tensor, query_id: torch.Tensor = None, product_i
         cat = torch.cat([outs[r, :c] for r, c in enumerate(counts)])
         all_q, all_p = cat[:, 0], cat[:, 1]
     return all_scores, all_q, all_p
+
+
+def reduce_ndcg(hist, evaluated, group=None):
+    """Sum the per-rank nDCG histograms (``ndcg.ndcg_device(..., allow_missing=True, return_hist=True)`` on each rank's query shard) over the
+    ranks: ONE SUM all-reduce of the int64 histogram with the evaluated-query count appended -- (k + 1) << k + 1 integers instead of the score
+    gather.  ``hist``: int64 numpy array or tensor (host or device; the result is a tensor of the same kind), ``evaluated``: int or 0-d tensor.
+    -> (hist, evaluated: int) identical on every rank.  Integer sums: the N-rank histogram equals the 1-rank histogram of the same scores exactly,
+    and so does ``ndcg.ndcg_from_hist`` of it.  The caller checks that ``evaluated`` equals the key length (every key query scored by one rank)."""
+    h = hist if torch.is_tensor(hist) else torch.from_numpy(np.ascontiguousarray(hist, np.int64))
+    buf = torch.cat([h.reshape(-1).to(torch.int64), torch.as_tensor(evaluated, dtype=torch.int64, device=h.device).reshape(1)])
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+        dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=group)
+    return buf[:-1], int(buf[-1])
