@@ -174,11 +174,11 @@ typedef struct mms_ensemble_batch {
 /* ABI revision of the structs and entry points declared in this header.  It changes whenever a struct gains a field or an entry
  * point changes its signature (r1: 1; r2 added mms_config.fuse_layernorm, mms_zk_batch.label_ids, mms_lxmert_batch.label_ids / x_norm
  * without bumping it; r3: 3, then 4 with mms_config.fuse_attention; r4: 5 -- mms_dbg_gemm takes the engine per call,
- * the process-global mms_set_gemm_variant and the lab engines' hooks left the product library, fuse_layernorm became a mask; r5: 6 -- mms_dbg_qkv_attn and mms_side_lane_flops added; r7: 7 -- mms_decode_feats_b64 added; r8: 8 -- mms_rank_workspace_bytes and mms_rank_submission added; r9: 9 -- mms_ndcg_workspace_bytes, mms_key_relevance and mms_ndcg_at_k added).  A caller built against another revision would make the library read past its structs, so compare
+ * the process-global mms_set_gemm_variant and the lab engines' hooks left the product library, fuse_layernorm became a mask; r5: 6 -- mms_dbg_qkv_attn and mms_side_lane_flops added; r7: 7 -- mms_decode_feats_b64 added; r8: 8 -- mms_rank_workspace_bytes and mms_rank_submission added; r9: 9 -- mms_ndcg_workspace_bytes, mms_key_relevance and mms_ndcg_at_k added; r10: 10 -- mms_ndcg_sweep_workspace_bytes and mms_ndcg_weight_sweep added).  A caller built against another revision would make the library read past its structs, so compare
  * BEFORE the first mms_create:  if (mms_version() != MMS_ABI_VERSION) abort();   (lib.py's load() does) */
-#define MMS_ABI_VERSION 9
+#define MMS_ABI_VERSION 10
 int mms_version(void);
-const char* mms_global_error(void);              /* message of the last failing mms_create / mms_decode_feats_b64 / mms_rank_submission / mms_key_relevance / mms_ndcg_at_k */
+const char* mms_global_error(void);              /* message of the last failing mms_create / mms_decode_feats_b64 / mms_rank_submission / mms_key_relevance / mms_ndcg_at_k / mms_ndcg_weight_sweep */
 
 int mms_create(const mms_config* cfg, mms_handle** out);
 void mms_destroy(mms_handle* h);
@@ -332,6 +332,42 @@ int mms_ndcg_at_k(const int64_t* query_id, const int64_t* product_id, const floa
                   const int64_t* key_query, const int64_t* key_off, const int64_t* key_product, int64_t n_key_queries, int64_t n_key_products,
                   int32_t k, int32_t allow_missing, void* workspace, int64_t workspace_bytes, int32_t* out_code /* [n_key_queries] */,
                   int64_t* out_topk /* [n_key_queries][k] or NULL */, int64_t* hist /* [(k + 1) << k] */, int32_t* status /* [4] */, void* stream);
+
+/* Fitting the ensemble weights on the valid set: the nDCG@k histogram -- and, optionally, the value -- of EVERY weight vector of a grid in one
+ * call, over the member scores mms_score_ensemble leaves on the device.  Rows, answer key, k, allow_missing, status words and flag bits are
+ * those of mms_ndcg_at_k; the score is replaced by n_members member scores, member-major in fp32 (members[m * n + r]: the member_scores layout
+ * of mms_score_ensemble), and n_weights weight vectors (weights[v * n_members + m], device fp64).
+ *   ARITHMETIC CONTRACT.  For weight vector v and row r
+ *       score_v[r] = (...((w[v][0] * s0) + w[v][1] * s1) + ...) + w[v][n_members - 1] * s_{n_members - 1}
+ *   in IEEE double: the members widened exactly, every product and every sum rounded on its own, left to right -- Python's evaluation of
+ *   code/main.py:59, numpy's when written as separate ufunc calls; never a fused multiply-add.  hist_out[v] is by definition the histogram
+ *   mms_ndcg_at_k yields for score_f64 = score_v: rows ranked by (image descending, row ascending) with -0.0 == +0.0, code = mask | ideal << 8,
+ *   hist_out[v][ideal << k | mask] += 1 over the key queries that have rows ((k + 1) << k int64 bins per vector, zeroed by the call).
+ *       value_out[v] = (sum over ALL bins b in bin order of double(hist_out[v][b]) * bin_value[b]) / n_key_queries_total
+ *   each product, each sum and the division rounded on its own.  bin_value is the caller's table of the per-code nDCG (ndcg._code_value: the
+ *   metric's arithmetic stays in one place), so value_out[v] is ndcg.ndcg_from_hist(hist_out[v], k, n_key_queries_total) bit for bit (an empty
+ *   bin adds +0.0 to a non-negative sum).  value_out may be NULL; given, it needs bin_value and n_key_queries_total >= 1.
+ *   A non-finite score_v[r] of a row that belongs to a key query sets flag bit 1 (a row outside the key is never read).  With a weight of 0 a
+ *   member of +-inf gives NaN, as in Python.
+ *   The value at w = (0.2, 0.2, 0.3, 0.3) is the DOUBLE merge of main.py; the merged output of mms_score_ensemble is the fp32 merge, whose
+ *   ranking can differ on a near tie.
+ *   workspace: device memory, 256-byte aligned, at least mms_ndcg_sweep_workspace_bytes(n, n_key_queries, n_key_products, n_members) bytes.
+ * The score-independent stages of mms_ndcg_at_k (key tables, relevance of every row, scan, scatter) run once per call; then a wavefront takes a
+ * key query and a tile of 64 weight vectors, a lane owning one vector (csrc/ndcg_sweep.hip).  Integer atomics only: equal inputs give bit-equal
+ * outputs.  ONLY ENQUEUES on `stream` (fills and at most ten kernels): no allocation, no synchronisation, no device -> host read.  Handle-free.
+ * Returns MMS_ERR_ARG (message in mms_global_error, nothing launched) for a count that is negative or over its cap (those of mms_ndcg_at_k;
+ * n_members in 1..MMS_SWEEP_MAX_MEMBERS, n_weights <= MMS_SWEEP_MAX_WEIGHTS), k outside 1..MMS_NDCG_MAX_K, a NULL pointer whose count is non-zero
+ * (status: always), value_out without bin_value, a workspace that is too small or not 256-byte aligned (needed when n_key_queries > 0).
+ * n == 0, n_key_queries == 0: zero histograms, status as mms_ndcg_at_k (values 0); n_weights == 0: the status alone. */
+#define MMS_SWEEP_MAX_MEMBERS 8
+#define MMS_SWEEP_MAX_WEIGHTS (1 << 20)
+int64_t mms_ndcg_sweep_workspace_bytes(int64_t n, int64_t n_key_queries, int64_t n_key_products, int32_t n_members);   /* a multiple of 256; -1 outside the caps */
+int mms_ndcg_weight_sweep(const int64_t* query_id, const int64_t* product_id, const float* members /* [n_members][n] */, int32_t n_members, int64_t n,
+                          const int64_t* key_query, const int64_t* key_off, const int64_t* key_product, int64_t n_key_queries, int64_t n_key_products,
+                          const double* weights /* device [n_weights][n_members] */, int64_t n_weights, int32_t k, int32_t allow_missing,
+                          const double* bin_value /* device [(k+1)<<k] or NULL */, int64_t n_key_queries_total /* divisor of value_out */,
+                          void* workspace, int64_t workspace_bytes, int64_t* hist_out /* [n_weights][(k+1)<<k], zeroed by the call */,
+                          double* value_out /* [n_weights] or NULL; needs bin_value */, int32_t* status /* [4] as mms_ndcg_at_k */, void* stream);
 
 /* accumulated hipEvent time (ms) and launch count of the GEMM kernels since the last reset;
  * enable = 1 brackets every GEMM launch with events on its stream (bench / roofline only) */

@@ -285,3 +285,16 @@ long long ndcg_workspace_bytes(long long n, long long n_key_queries, long long n
 void launch_ndcg(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int n, const int64_t* key_query,
                  const int64_t* key_off, const int64_t* key_product, int Qa, int Tk, int k, int allow_missing, void* workspace, int64_t* labels_out,
                  int32_t* out_code, int64_t* out_topk, int64_t* hist, int32_t* status, hipStream_t st);
+// stages 1-7 of launch_ndcg alone (status fill, key tables, per-row key index and relevance, scan, scatter: nothing that reads a score), for a
+// caller that ranks the lists itself (ndcg_sweep.hip).  Qa > 0.  The views point into `workspace` (its first ndcg_workspace_bytes bytes):
+// key query i owns list[off[i] .. off[i] + cnt[i]) (row indices, in arbitrary order), rel[row] is 0 / 1, distinct[i] its distinct truth products;
+// status[1] = the rows listed, status[2] / [3] the flags and the missing key queries as in mms_ndcg_at_k.
+struct NdcgLists { const int* cnt; const int* off; const int* distinct; const int* list; const unsigned char* rel; };
+NdcgLists launch_ndcg_lists(const int64_t* query_id, const int64_t* product_id, int n, const int64_t* key_query, const int64_t* key_off,
+                            const int64_t* key_product, int Qa, int Tk, int allow_missing, void* workspace, int32_t* status, hipStream_t st);
+// ndcg_sweep.hip: nDCG@k histograms (and values) of n_weights weighted merges of n_members member scores (mms_ndcg_weight_sweep checks the arguments).
+long long ndcg_sweep_workspace_bytes(long long n, long long n_key_queries, long long n_key_products, int n_members);
+void launch_ndcg_sweep(const int64_t* query_id, const int64_t* product_id, const float* members, int n_members, int n, const int64_t* key_query,
+                       const int64_t* key_off, const int64_t* key_product, int Qa, int Tk, const double* weights, long long n_weights, int k,
+                       int allow_missing, const double* bin_value, long long n_key_queries_total, void* workspace, int64_t* hist_out, double* value_out,
+                       int32_t* status, hipStream_t st);

@@ -21,6 +21,7 @@
 //   k_select         one wavefront per key query: k rounds of a wave-wide arg-max over (image, row) below the previous pick, looping over
 //                    the list when it is longer than a wavefront
 // mms_key_relevance stops after k_scan_top (it needs the totals only).  No workgroup waits on another: the stages meet at kernel boundaries.
+// The weight sweep (ndcg_sweep.hip, mms_ndcg_weight_sweep) runs everything up to k_scatter with no score (launch_ndcg_lists) and ranks the lists itself.
 // The only atomics are integer add / or / compare-and-swap whose final memory value is independent of the arrival order, and the values they
 // return (a table slot, a list position) never reach an output: equal inputs give bit-equal outputs.
 #include "rank_tables.h"
@@ -265,15 +266,12 @@ __global__ __launch_bounds__(256) void k_select(const long long* pid, int Qa, in
 
 long long ndcg_workspace_bytes(long long n, long long Qa, long long Tk) { return (long long)ndcg_layout(nullptr, n, Qa, Tk).total_bytes; }
 
-void launch_ndcg(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int n, const int64_t* key_query,
-                 const int64_t* key_off, const int64_t* key_product, int Qa, int Tk, int k, int allow_missing, void* workspace, int64_t* labels_out,
-                 int32_t* out_code, int64_t* out_topk, int64_t* hist, int32_t* status, hipStream_t st) {
-    (void)hipMemsetAsync(status, 0, 16, st);
-    if (hist) (void)hipMemsetAsync(hist, 0, ((size_t)(k + 1) << k) * 8, st);
-    if (Qa <= 0) {                                                           // no key: no row belongs to a key query
-        if (labels_out && n > 0) (void)hipMemsetAsync(labels_out, 0, (size_t)n * 8, st);
-        return;
-    }
+namespace {
+// stages 1-7 (key tables, per-row key index and relevance, scan; with `lists` also list offsets and scatter): everything that reads no ranking.
+// score_f32 == score_f64 == nullptr: no score is read and no image is written.
+NdcgWs ndcg_stages(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int n, const int64_t* key_query,
+                   const int64_t* key_off, const int64_t* key_product, int Qa, int Tk, int allow_missing, void* workspace, int64_t* labels_out, bool lists,
+                   int32_t* status, hipStream_t st) {
     const NdcgWs w = ndcg_layout(workspace, n, Qa, Tk);
     (void)hipMemsetAsync(w.kqkey, 0xFF, w.ff_bytes, st);
     (void)hipMemsetAsync(w.cnt, 0, w.zero_bytes, st);
@@ -288,9 +286,33 @@ void launch_ndcg(const int64_t* query_id, const int64_t* product_id, const float
     }
     hipLaunchKernelGGL(k_scan_sums, scan, block, 0, st, Qa, w);
     hipLaunchKernelGGL(k_scan_top, dim3(1), block, 0, st, (int)scan.x, Qa, allow_missing, w, status);
-    if (!out_code) return;                                                   // mms_key_relevance: labels and totals only
+    if (!lists) return w;                                                    // mms_key_relevance: labels and totals only
     hipLaunchKernelGGL(k_scan_apply, scan, block, 0, st, Qa, w);
     if (n > 0) hipLaunchKernelGGL(k_scatter, rows, block, 0, st, n, w);
+    return w;
+}
+}  // namespace
+
+void launch_ndcg(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int n, const int64_t* key_query,
+                 const int64_t* key_off, const int64_t* key_product, int Qa, int Tk, int k, int allow_missing, void* workspace, int64_t* labels_out,
+                 int32_t* out_code, int64_t* out_topk, int64_t* hist, int32_t* status, hipStream_t st) {
+    (void)hipMemsetAsync(status, 0, 16, st);
+    if (hist) (void)hipMemsetAsync(hist, 0, ((size_t)(k + 1) << k) * 8, st);
+    if (Qa <= 0) {                                                           // no key: no row belongs to a key query
+        if (labels_out && n > 0) (void)hipMemsetAsync(labels_out, 0, (size_t)n * 8, st);
+        return;
+    }
+    const NdcgWs w = ndcg_stages(query_id, product_id, score_f32, score_f64, n, key_query, key_off, key_product, Qa, Tk, allow_missing, workspace, labels_out,
+                                 out_code != nullptr, status, st);
+    if (!out_code) return;
     const int sel_blocks = (int)std::min<long long>(2048, ((long long)Qa + 3) / 4);
-    hipLaunchKernelGGL(k_select, dim3(sel_blocks), block, 0, st, p, Qa, k, w, out_code, (long long*)out_topk, (u64*)hist);
+    hipLaunchKernelGGL(k_select, dim3(sel_blocks), dim3(256), 0, st, (const long long*)product_id, Qa, k, w, out_code, (long long*)out_topk, (u64*)hist);
+}
+
+NdcgLists launch_ndcg_lists(const int64_t* query_id, const int64_t* product_id, int n, const int64_t* key_query, const int64_t* key_off,
+                            const int64_t* key_product, int Qa, int Tk, int allow_missing, void* workspace, int32_t* status, hipStream_t st) {
+    (void)hipMemsetAsync(status, 0, 16, st);
+    const NdcgWs w = ndcg_stages(query_id, product_id, nullptr, nullptr, n, key_query, key_off, key_product, Qa, Tk, allow_missing, workspace, nullptr, true,
+                                 status, st);
+    return NdcgLists{w.cnt, w.off, w.distinct, w.list, w.rel};
 }

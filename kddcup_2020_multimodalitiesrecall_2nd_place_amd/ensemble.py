@@ -219,3 +219,64 @@ def write_submission(path, rows):
         w.writerow(["query-id", "product1", "product2", "product3", "product4", "product5"])
         for q, ps in rows.items():
             w.writerow([q] + list(ps))
+
+
+def weight_grid(members: int = 4, steps: int = 20):
+    """The simplex grid of step ``1 / steps``: float64 [C(steps + members - 1, members - 1), members], the rows ``np.array(c, float64) / steps`` for
+    the integer compositions ``c`` of ``steps`` into ``members`` non-negative parts, in lexicographic order ((0, .., 0, steps) first,
+    (steps, 0, .., 0) last).  4 members: 35 rows at steps = 4, 1 771 at 20, 176 851 at 100."""
+    import numpy as np
+    if members < 1 or steps < 1:
+        raise ValueError("weight_grid: members and steps must be >= 1")
+    rows, c = [], [0] * members
+
+    def fill(i, left):
+        if i == members - 1:
+            c[i] = left
+            rows.append(tuple(c))
+            return
+        for x in range(left + 1):
+            c[i] = x
+            fill(i + 1, left - x)
+
+    fill(0, steps)
+    return np.array(rows, np.float64) / steps
+
+
+def fit_weights(query_id, product_id, members, rank_label, grid=None, k: int = 5, allow_missing: bool = False, where: str = "device", info: dict = None):
+    """The ensemble weights as a result of the valid set: nDCG@k of the merge ``(...(w0 * s0 + w1 * s1) + ...)`` (``ndcg.merge_members``: IEEE double,
+    every operation rounded on its own, main.py:59's evaluation) for every row ``w`` of ``grid`` (default ``weight_grid(M, 20)``), and the winner --
+    the FIRST grid row that attains the maximum.  ``members``: fp32 [M, n], member-major (a device tensor stays where it is).
+    -> (weights tuple, value, index, values float64 numpy [W]).
+    ``where="device"``: ``ndcg.ndcg_sweep_device`` (``mms_ndcg_weight_sweep``: one call for the whole grid); ONE synchronising read carries the
+    status and the values.  What the device does not do -- a non-finite merged score of a key query's row, a repeated key query, a reserved id --
+    it detects: the values then come from ``ndcg.ndcg_sweep_host``, which ``where="host"`` runs directly; both give the same floats, bit for bit.
+    A key query without rows raises ``KeyError`` unless ``allow_missing``.  ``info`` (a dict) receives ``{"path": "device" | "host", "flags": int}``."""
+    import numpy as np
+
+    from . import ndcg
+    if where not in ("host", "device"):
+        raise ValueError("where must be 'host' or 'device', not %r" % (where,))
+    label_dict = rank_label.rank_label if isinstance(rank_label, ndcg.AnswerKey) else rank_label
+    M = len(members)
+    grid = weight_grid(M, 20) if grid is None else np.ascontiguousarray(grid, np.float64)
+    if grid.ndim != 2 or grid.shape[0] == 0:
+        raise ValueError("fit_weights: the grid must be [W >= 1, %d]" % M)
+    values, flags = None, 0
+    if where == "device" and len(label_dict):
+        import torch
+        dvalues, _, status = ndcg.ndcg_sweep_device(query_id, product_id, members, grid, rank_label, k, allow_missing)
+        host = torch.cat([status.to(torch.float64), dvalues]).cpu().numpy()      # the one synchronising read
+        flags = int(host[2])
+        if flags & ~ndcg.FLAG_MISSING_QUERY == 0:
+            if flags & ndcg.FLAG_MISSING_QUERY:                                  # only without allow_missing
+                raise KeyError("%d key queries have no rows" % int(host[3]))
+            values = host[4:].copy()
+    if info is not None:
+        info.update(path="device" if values is not None else "host", flags=flags)
+    if values is None:
+        to_np = lambda x: x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+        mem = np.stack([to_np(m) for m in members]) if isinstance(members, (list, tuple)) else to_np(members)
+        values, _ = ndcg.ndcg_sweep_host(to_np(query_id), to_np(product_id), mem, grid, label_dict, k, allow_missing)
+    index = int(np.argmax(values))                                               # the first row that attains the maximum
+    return tuple(float(x) for x in grid[index]), float(values[index]), index, values

@@ -258,3 +258,99 @@ def ndcg_device(query_id, product_id, score, rank_label, k: int = 5, info: dict 
     if return_hist:
         return body.copy(), int(host[0])
     return ndcg_from_codes(body, k)
+
+
+# ---- weight sweep: the histogram and the value of EVERY weight vector of a grid (mms_ndcg_weight_sweep, csrc/ndcg_sweep.hip) ----
+MAX_MEMBERS, MAX_WEIGHTS = 8, 1 << 20                                                      # MMS_SWEEP_MAX_MEMBERS, MMS_SWEEP_MAX_WEIGHTS
+_BIN_TABLES: dict = {}
+
+
+def bin_values(k: int = 5):
+    """float64 [(k + 1) << k]: the nDCG@k of a key query per histogram bin (``_code_value`` of the bin's code) -- the table ``mms_ndcg_weight_sweep``
+    takes as ``bin_value``.  Read-only, built once per k (its device copies are kept beside it, per (k, device))."""
+    if k not in _BIN_TABLES:
+        t = np.array([_code_value((b >> k) << 8 | (b & ((1 << k) - 1)), k) for b in range((k + 1) << k)], np.float64)
+        t.setflags(write=False)
+        _BIN_TABLES[k] = t
+    return _BIN_TABLES[k]
+
+
+def merge_members(members, w):
+    """``(...((w[0] * s0) + w[1] * s1) + ...) + w[M - 1] * s_{M-1}`` in float64, each product and each sum a numpy operation of its own (rounded on
+    its own, left to right): Python's evaluation of code/main.py:59 -- the arithmetic contract of the sweep.  ``members``: float32 [M, n]."""
+    acc = np.float64(w[0]) * members[0].astype(np.float64)
+    for m in range(1, len(members)):
+        prod = np.float64(w[m]) * members[m].astype(np.float64)
+        acc = acc + prod
+    return acc
+
+
+def _sweep_args(members, weights, k):
+    if not 1 <= k <= MAX_K:
+        raise ValueError("k must be in 1..%d" % MAX_K)
+    M = int(members.shape[0]) if members.ndim == 2 else 0
+    if not 1 <= M <= MAX_MEMBERS:
+        raise ValueError("members must be [1..%d, n], not %s" % (MAX_MEMBERS, tuple(members.shape)))
+    if weights.ndim != 2 or weights.shape[1] != M:
+        raise ValueError("weights must be [W, %d], not %s" % (M, tuple(weights.shape)))
+    if weights.shape[0] > MAX_WEIGHTS:
+        raise ValueError("at most %d weight vectors per call" % MAX_WEIGHTS)
+
+
+def ndcg_sweep_host(query_id, product_id, members, weights, rank_label: dict, k: int = 5, allow_missing: bool = False):
+    """The host form of the sweep and the reference of the device form: per weight vector ``hist_from_codes(ndcg_codes(q, p, merge_members(members,
+    w), ...))`` and ``ndcg_from_hist`` of it over the whole key.  ``members``: float32 [M, n] (member-major, the layout ``mms_score_ensemble`` writes),
+    ``weights``: float64 [W, M].  -> (values float64 [W], hist int64 [W, (k + 1) << k]), numpy."""
+    mem = np.stack([np.asarray(m).reshape(-1) for m in members]) if isinstance(members, (list, tuple)) and members else np.asarray(members)
+    mem = mem.astype(np.float32) if mem.dtype != np.float32 else mem
+    wts = np.asarray(weights, np.float64)
+    _sweep_args(mem, wts, k)
+    label_dict = rank_label.rank_label if isinstance(rank_label, AnswerKey) else rank_label
+    mem = mem.reshape(mem.shape[0], -1)
+    values = np.empty(wts.shape[0], np.float64)
+    hist = np.empty((wts.shape[0], (k + 1) << k), np.int64)
+    for v in range(wts.shape[0]):
+        hist[v] = hist_from_codes(ndcg_codes(query_id, product_id, merge_members(mem, wts[v]), label_dict, k, allow_missing), k)
+        values[v] = ndcg_from_hist(hist[v], k, len(label_dict))
+    return values, hist
+
+
+def ndcg_sweep_device(query_id, product_id, members, weights, rank_label, k: int = 5, allow_missing: bool = False):
+    """``mms_ndcg_weight_sweep``: the sweep on the GPU in one call.  ``members`` [M, n] fp32 and ``weights`` [W, M] fp64 are used in place when they
+    are contiguous device tensors of that dtype (the member scores stay where ``mms_score_ensemble`` left them), host arrays are copied up once;
+    ``rank_label``: the ``{query: [products]}`` dict or an ``AnswerKey``.  -> (values float64 [W], hist int64 [W, (k + 1) << k], status int32 [4]),
+    device tensors, bit-equal to ``ndcg_sweep_host`` while the flag word ``status[2]`` is zero (or "missing" alone with ``allow_missing``).
+    Only enqueues on the current stream: nothing is read back, nothing waits."""
+    import torch
+
+    from . import lib as _lib
+    (q, p), dev = _rows_on_device((query_id, product_id), ((torch.int64,), (torch.int64,)), "ndcg_sweep_device")
+    to_t = lambda x, dt: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).to(device=dev, dtype=dt, non_blocking=True).contiguous()
+    if isinstance(members, (list, tuple)):
+        members = torch.stack([to_t(m, torch.float32).reshape(-1) for m in members]) if members else torch.zeros((0, 0))
+    mem, wts = to_t(members, torch.float32), to_t(weights, torch.float64)
+    _sweep_args(mem, wts, k)
+    n, M, W = q.shape[0], mem.shape[0], wts.shape[0]
+    if mem.shape[1] != n:
+        raise ValueError("ndcg_sweep_device: %d rows, member scores of %d" % (n, mem.shape[1]))
+    key = _key_on(rank_label, dev)
+    if key.n_queries == 0:
+        raise ValueError("ndcg_sweep_device: empty answer key")
+    l = _lib.load()
+    ws_bytes = l.mms_ndcg_sweep_workspace_bytes(n, key.n_queries, key.n_products, M)
+    if ws_bytes < 0:
+        raise ValueError("ndcg_sweep_device: %d rows, %d key queries, %d key products: the device path takes at most 2^22 rows / key products and 2^20 "
+                         "key queries" % (n, key.n_queries, key.n_products))
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    if (k, dev) not in _BIN_TABLES:
+        _BIN_TABLES[k, dev] = torch.from_numpy(bin_values(k).copy()).to(dev)
+    table = _BIN_TABLES[k, dev]
+    hist = torch.empty((W, (k + 1) << k), dtype=torch.int64, device=dev)
+    values = torch.empty((W,), dtype=torch.float64, device=dev)
+    status = torch.empty((4,), dtype=torch.int32, device=dev)
+    rc = l.mms_ndcg_weight_sweep(_ptr(q), _ptr(p), _ptr(mem), M, n, _ptr(key.key_query), _ptr(key.key_off), _ptr(key.key_product), key.n_queries,
+                                 key.n_products, _ptr(wts), W, k, int(bool(allow_missing)), table.data_ptr(), key.n_queries, ws.data_ptr(), ws_bytes,
+                                 _ptr(hist), _ptr(values), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise _lib.MmsError("mms_ndcg_weight_sweep failed (%d): %s" % (rc, l.mms_global_error().decode()))
+    return values, hist, status

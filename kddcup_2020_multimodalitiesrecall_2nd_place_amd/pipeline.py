@@ -385,10 +385,18 @@ class EnsembleScorer:
 
     WEIGHTS = (0.2, 0.2, 0.3, 0.3)
 
-    def __init__(self, zk, lds, lxmert):
+    def __init__(self, zk, lds, lxmert, weights=None):
         from .scorers import EnsembleScorer as Fused
         self.zk, self.lds, self.lxmert = zk, lds, lxmert
-        self.fused = Fused(zk, lds, lxmert, self.WEIGHTS)
+        self.fused = Fused(zk, lds, lxmert, self.WEIGHTS if weights is None else weights)
+
+    @property
+    def weights(self):
+        return self.fused.weights
+
+    def set_weights(self, w):
+        """The merge weights of the following passes (``scorers.EnsembleScorer.set_weights``), e.g. the winner of ``fit_weights_tsv_native``."""
+        self.fused.set_weights(w)
 
     def _score(self, zk_feed, s2f_feed, lx_feed):
         merged, mem = self.fused(ensemble_feed(zk_feed, s2f_feed, lx_feed))
@@ -455,6 +463,27 @@ class EnsembleScorer:
         if scores_out is not None:
             scores_out.update(query_id=qid, product_id=pid, score=score)
         return _metric(qid, pid, score, rank_label, k, metric, False, info)
+
+    def fit_weights_tsv_native(self, tsv_path, vocab_path, label_table, rank_label, grid=None, k: int = 5, labels: str = "answer",
+                               batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host", info: dict = None, scores_out: dict = None):
+        """A valid TSV file -> the merge weights that maximise nDCG@k against the answer key: ONE pass of ``evaluate_tsv_native`` with the four member
+        scores left on the device, then ``ensemble.fit_weights`` over ``grid`` (default ``ensemble.weight_grid(4, 20)``, 1 771 vectors) in one
+        library call (``mms_ndcg_weight_sweep``).  -> (weights tuple, value, index, values numpy [W]), the tuple of ``fit_weights``.
+        The scorer's own weights are NOT changed: call ``set_weights(best)`` before the testB pass.  ``labels``: the zk members' label feed, as
+        in ``evaluate_tsv_native``.  ``scores_out`` (a dict) receives ``query_id`` / ``product_id`` (numpy) and ``members`` (device fp32 [4, n]).
+        The value of a weight vector is that of main.py's DOUBLE merge of the fp32 member scores; ``evaluate_tsv_native`` ranks the fp32 merge
+        of the fused call, which can differ on a near tie."""
+        from . import ensemble, ndcg
+        _check_eval_args("device", labels)
+        relabel = None
+        if labels == "answer":
+            rank_label = rank_label if isinstance(rank_label, ndcg.AnswerKey) else ndcg.AnswerKey(rank_label, self.zk.device)
+            relabel = _answer_labels(rank_label)
+        qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=True, relabel=relabel)
+        mem = torch.cat([m for _, m in out], 1) if out else torch.zeros((4, 0), dtype=torch.float32, device=self.zk.device)
+        if scores_out is not None:
+            scores_out.update(query_id=qid, product_id=pid, members=mem)
+        return ensemble.fit_weights(qid, pid, mem, rank_label, grid, k, info=info)
 
     def score_tsv_native(self, tsv_path, vocab_path, label_table, batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host"):
         """``score_lines`` on a TSV file through libmmfeat, decode and scoring overlapped: a producer thread decodes span batch i+1

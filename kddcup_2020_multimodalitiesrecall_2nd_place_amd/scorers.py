@@ -339,8 +339,17 @@ class EnsembleScorer:
     def __init__(self, zk: "ZkScorer", lds: "LdsScorer", lxmert: "LxmertScorer", weights=WEIGHTS):
         self.zk, self.lds, self.lxmert = zk, lds, lxmert
         self.device = zk.device
-        self.w = (_lib.C.c_float * 4)(*weights)
+        self.set_weights(weights)
         self.lib = _lib.load()
+
+    def set_weights(self, w):
+        """The four merge weights of the following calls (zk, zk on the sen2forest rewrite, lds, lxmert) -- e.g. ``ensemble.fit_weights``'s winner
+        on the valid set instead of main.py:59's constants."""
+        w = tuple(float(x) for x in w)
+        if len(w) != 4:
+            raise ValueError("the ensemble merges four members, not %d" % len(w))
+        self.weights = w
+        self.w = (_lib.C.c_float * 4)(*w)
 
     def prepare(self, feed: dict):
         """feed keys (numpy or torch, any integer dtype): feats [B,10,2048], boxes_5 [B,10,5], num_boxes [B], label_ids
