@@ -412,8 +412,33 @@ int mms_dbg_gemm(const float* a_f32, int64_t M, int64_t K, int64_t lda, const fl
 /* fp8 GEMM (precision 4, MX-scaled fp8 MFMA) on fp32 operands: A and W are quantised exactly as the forward does it (A: e4m3 RNE of the
  * value; W: per output channel the smallest POWER OF TWO scale with max|w| / scale <= 448, e4m3 RNE of w / scale; the scale is applied
  * by the MFMA instruction itself as the weight operand's e8m0 hardware scale).  N % 256 == 0, K % 128 == 0 */
+/* The output addressing of a launch, opened up for the kernel tests (tests/test_gemm_addressing_gpu.py; the numpy statement of these fields is
+ * tests/helpers.py gemm_rows_ref).  A row map {grp, stride, off} sends logical row r to physical row (r / grp) * stride + off + r % grp; grp == 0 is the
+ * identity.  mms_dbg_gemm_rows reads every field; the hooks that take an OPTIONAL mms_rows_spec name the fields they read. */
+typedef struct mms_rows_spec {
+    int32_t M, N, K;
+    int32_t nsplit;        /* 1, 2, 3: the precision modes of mms_dbg_gemm */
+    int32_t engine;        /* ONE named engine (enum Engine), launched through its own launcher: a shape or field set it refuses is MMS_ERR_ARG, no fall-back */
+    int32_t act, reverse;
+    int32_t m_live;        /* >= 0: the device-side live-row count (rows >= min(M, m_live) are not written); -1: none */
+    int32_t a_rows, lda;   /* A: fp32 [a_rows][lda], lda >= K, lda % 32 == 0 */
+    int32_t amap[3];       /* logical row -> A row (ignored when a_index is given) */
+    int32_t r_rows;        /* residual: fp32 [r_rows][N] */
+    int32_t rmap[3];       /* logical row -> residual row (ignored when r_index is given) */
+    int32_t out_kind;      /* 0: fp32 [c_rows][ldo], ldo >= N, ldo % 4 == 0;  1: split planes [c_rows][ldo], ldo >= N, ldo % 32 == 0, passed and returned as
+                            * their fp32 image;  2: head-major fp32 [hm_blocks][hm_rows][64]: columns [64 g, 64 g + 64) of a row go to block hm_col0 / 64 + g */
+    int32_t ldo, c_rows;
+    int32_t cmap[3];       /* logical row -> output row (of c_rows, or of hm_rows for out_kind 2) */
+    int32_t hm_rows, hm_col0, hm_blocks;     /* out_kind 2: hm_col0 % 64 == 0, (hm_col0 + N) / 64 <= hm_blocks */
+} mms_rows_spec;
 int mms_dbg_gemm_f8(const float* a_f32, int64_t M, int64_t K, const float* w_f32_nk, int64_t N, const float* bias, int32_t act,
                     int32_t out_f8, float* c_f32, void* stream);
+/* ... with `rows` (NULL = the dense call above): m_live, cmap, c_rows, ldo and -- with out_f8 == 0 -- out_kind 0 / 2 with hm_rows / hm_col0 / hm_blocks are
+ * honoured; with out_f8 the e4m3 bytes are [c_rows][ldo], ldo % 32 == 0 (GemmParams::ldf8).  c_f32 is then the caller's PRE-FILLED physical image (for out_f8 it is
+ * rounded to e4m3 bytes before the launch and the whole byte buffer is decoded back after it); every output row a logical row r < M can address is checked
+ * against it on the host */
+int mms_dbg_gemm_f8_rows(const float* a_f32, int64_t M, int64_t K, const float* w_f32_nk, int64_t N, const float* bias, int32_t act,
+                         int32_t out_f8, float* c_f32, const mms_rows_spec* rows, void* stream);
 /* out = LayerNorm(A W^T + bias + resid) over N = 768 through the GEMM with the fused LayerNorm epilogue (gemm_pp_ln.h) and the
  * LayerNorm kernel queued behind it; *mode_out = 1 when the launch ran fused, 2 when it took the plain two-kernel route */
 int mms_dbg_gemm_ln(const float* a_f32, int64_t M, int64_t K, const float* w_f32_nk, const float* bias, const float* resid_f32,
@@ -424,6 +449,11 @@ int mms_dbg_gemm_ln(const float* a_f32, int64_t M, int64_t K, const float* w_f32
  * partials from the skinny kernel instead (K slices dealt to workgroups, M <= 512): bit-identical to the tile engine's */
 int mms_dbg_proj_ln_splitk(const float* a_f32, int64_t M, int64_t K, const float* w_f32_nk, const float* bias, const float* resid_f32,
                            const float* gamma, const float* beta, int32_t splits, float* c_f32, void* stream);
+int mms_dbg_proj_ln_splitk_rows(const float* a_f32, int64_t M, int64_t K, const float* w_f32_nk, const float* bias, const float* resid_f32,
+                                const float* gamma, const float* beta, int32_t splits, float* c_f32,
+                                const mms_rows_spec* rows /* optional: a_f32 is [a_rows][lda] read through amap / a_index (the split-K GEMM), resid_f32 [r_rows][768] read
+ * through rmap / r_index (the LayerNorm that sums the partials); every row a logical row r < M can address is checked on the host */,
+                                const int32_t* a_index, const int32_t* r_index, void* stream);
 /* time one GEMM shape on random data (`what`: an engine as in mms_dbg_gemm, or 52: the MX-fp8 engine; 60 / 61: the LayerNorm kernel with / without
  * residual; 62 / 63: N = 768 projection + residual + LayerNorm as two kernels / as one launch with the fused epilogue -- api.hip enum BenchMode) */
 int mms_dbg_gemm_bench(int64_t M, int64_t N, int64_t K, int32_t nsplit, int32_t act, int32_t out_planes, int32_t resid,
@@ -479,6 +509,9 @@ int mms_dbg_dedup(int32_t kind, const void* ids, const int64_t* mask, int32_t T,
  * written).  The planes and the bytes are zero-filled first */
 int mms_dbg_layernorm_ex(const float* x, const float* gamma, const float* beta, int64_t M, const float* resid_f32, int64_t resid_rows, const int32_t* r_index,
                          int64_t m_live, int32_t flags, float* out_f32, float* out_f8, void* stream);
+int mms_dbg_layernorm_rows(const float* x, const float* gamma, const float* beta, int64_t M, const float* resid_f32, int64_t resid_rows, const int32_t* r_index,
+                           int64_t m_live, int32_t flags, float* out_f32, float* out_f8,
+                           const int32_t* rmap /* optional host {grp, stride, off}: without r_index the residual row of row r is LnResid::rmap(r), checked on the host */, void* stream);
 /* mms_dbg_gemm (two-pass bf16 planes, no residual) with a device-side live-row count and the head-major output of the QKV projections: m_live >= 0: rows >=
  * min(M, m_live) are not written, < 0: none.  out_kind 0: c_f32 [M][N]; 1: split planes, joined to fp32 [M][N]; 2: head-major fp32 [N / 64][M][64].
  * reverse 1: the tiles are walked from the last row tile down, as every second big launch of a forward walks them (the ragged tile first).  c_f32 is zero-filled first */
@@ -487,6 +520,18 @@ int mms_dbg_gemm_ex(const float* a_f32, int64_t M, int64_t K, const float* w_f32
 /* one conversion launcher on n elements (n % 32 == 0).  kind 0: fp32 -> e4m3 bytes; 1: e4m3 bytes -> fp32; 2: fp32 -> split planes -> fp32 (round trip);
  * 3: fp32 -> split planes -> e4m3 bytes */
 int mms_dbg_convert(int32_t kind, const void* in, void* out, int64_t n, void* stream);
+/* ONE GEMM launch with the six addressing fields of GemmParams as a forward sets them: C[cmap(r)] = act(A[a_index ? a_index[r] : amap(r)] W^T + bias
+ * (+ resid[r_index ? r_index[r] : rmap(r)])) for r < min(M, m_live).  a_index / r_index: device int32 [M] or NULL; resid_f32 NULL: no residual.  c_f32 is the
+ * caller's PRE-FILLED physical output (mms_rows_spec::out_kind) and is never cleared: for planes its fp32 image is split into the plane buffer before the launch and
+ * the WHOLE buffer is joined back after it, so the caller sees every element the kernel did or did not touch.  Before anything is launched the host checks that
+ * every A row, residual row and output row (head-major: every block) that a logical row r < M -- M, not m_live -- can address lies inside the buffers the spec
+ * describes: MMS_ERR_ARG otherwise, and MMS_ERR_ARG with c_f32 untouched when the named engine's launcher refuses the launch */
+int mms_dbg_gemm_rows(const mms_rows_spec* spec, const float* a_f32, const int32_t* a_index, const float* w_f32_nk, const float* bias,
+                      const float* resid_f32, const int32_t* r_index, float* c_f32, void* stream);
+/* k_splitk_reduce alone: out = act(sum_s parts[s] + bias), parts device fp32 [S][M][N] (N % 4 == 0), rows r < min(M, m_live) (m_live < 0: M).  out_kind / ldo /
+ * c_rows / hm_rows / hm_col0 / hm_blocks as in mms_rows_spec (the kernel has no row map: c_rows, hm_rows >= M); c_f32 is the caller's pre-filled physical image */
+int mms_dbg_splitk_reduce(const float* parts, int32_t S, int64_t M, int64_t N, const float* bias, int32_t act, int64_t m_live, int32_t out_kind,
+                          int32_t ldo, int64_t c_rows, int32_t hm_rows, int32_t hm_col0, int32_t hm_blocks, float* c_f32, void* stream);
 #endif /* MMS_TEST_HOOKS */
 
 #ifdef __cplusplus

@@ -9,6 +9,7 @@
 #include <unordered_map>
 #include <vector>
 
+#define MMS_TEST_HOOKS      // the test hooks defined at the end of this file: their prototypes and mms_rows_spec
 #include "../../include/mmscore.h"
 #include "kernels.h"
 
@@ -2353,6 +2354,47 @@ int mms_debug_read_x(mms_handle* h, float* dst_dev, int64_t rows, void* stream) 
 static int dbg_fail(const char* m) { g_err = m; return MMS_ERR_HIP; }
 #define DBG_TRY(expr) do { if ((expr) != hipSuccess) return dbg_fail(#expr); } while (0)
 
+// device buffers of one hook call, freed on every way out
+struct DbgPool {
+    std::vector<void*> p;
+    ~DbgPool() { for (void* q : p) (void)hipFree(q); }
+    void* get(size_t bytes) {
+        void* q = nullptr;
+        if (hipMalloc(&q, bytes ? bytes : 4) != hipSuccess) return nullptr;
+        p.push_back(q);
+        return q;
+    }
+};
+
+// ---- host-side checks of the addressing hooks (mms_rows_spec): nothing is launched until every row a launch can address lies inside its buffer ----
+static inline int64_t dbg_rowmap(const int32_t m[3], int64_t r) { return m[0] ? (r / m[0]) * (int64_t)m[1] + m[2] + r % m[0] : r; }
+static inline RowMap dbg_rowmap_dev(const int32_t m[3]) { return m[0] ? RowMap{m[0], m[1], m[2]} : RowMap{0, 0, 0}; }
+// every logical row r < M (the padded bound, not the live count) maps into [0, rows): through the device index when there is one, else through the map
+static bool dbg_rows_inside(const int32_t m[3], const int32_t* index_dev, int64_t M, int64_t rows) {
+    if (rows <= 0) return false;
+    if (index_dev) {
+        std::vector<int32_t> h((size_t)M);
+        if (hipMemcpy(h.data(), index_dev, (size_t)M * 4, hipMemcpyDeviceToHost) != hipSuccess) return false;
+        for (int32_t v : h) if (v < 0 || v >= rows) return false;
+        return true;
+    }
+    if (m[0] < 0) return false;
+    for (int64_t r = 0; r < M; ++r) { const int64_t v = dbg_rowmap(m, r); if (v < 0 || v >= rows) return false; }
+    return true;
+}
+// the physical output image of a spec: elements, or -1 when the spec's output fields contradict each other / a row r < M leaves the image
+static int64_t dbg_out_elems(int32_t out_kind, int64_t M, int64_t N, int32_t ldo, int64_t c_rows, const int32_t cmap[3], int32_t hm_rows, int32_t hm_col0, int32_t hm_blocks) {
+    if (out_kind == 2) {
+        if (N % 64 || hm_rows <= 0 || hm_blocks <= 0 || hm_col0 < 0 || hm_col0 % 64 || (hm_col0 + N) / 64 > hm_blocks) return -1;
+        if (!dbg_rows_inside(cmap, nullptr, M, hm_rows)) return -1;
+        return (int64_t)hm_blocks * hm_rows * 64;
+    }
+    if (out_kind != 0 && out_kind != 1) return -1;
+    if (c_rows <= 0 || ldo < N || ldo % (out_kind == 1 ? 32 : 4) || c_rows * (int64_t)ldo > (1ll << 31)) return -1;
+    if (!dbg_rows_inside(cmap, nullptr, M, c_rows)) return -1;
+    return c_rows * (int64_t)ldo;
+}
+
 int mms_dbg_gemm(const float* a_f32, int64_t M, int64_t K, int64_t lda, const float* w_f32_nk, int64_t N, const float* bias,
                  const float* resid_f32, int32_t act, int32_t nsplit, int32_t out_planes, int32_t engine, float* c_f32, void* stream) {
     if (!a_f32 || !w_f32_nk || !c_f32 || M <= 0 || N % 128 || K % 64 || lda < K || lda % 32 || engine < 0) { g_err = "mms_dbg_gemm: bad argument"; return MMS_ERR_ARG; }
@@ -2389,29 +2431,53 @@ int mms_dbg_gemm(const float* a_f32, int64_t M, int64_t K, int64_t lda, const fl
 
 int mms_dbg_gemm_f8(const float* a_f32, int64_t M, int64_t K, const float* w_f32_nk, int64_t N, const float* bias, int32_t act,
                     int32_t out_f8, float* c_f32, void* stream) {
-    if (!a_f32 || !w_f32_nk || !c_f32 || M <= 0 || N % 256 || K % 128) { g_err = "mms_dbg_gemm_f8: bad argument (N % 256, K % 128)"; return MMS_ERR_ARG; }
+    return mms_dbg_gemm_f8_rows(a_f32, M, K, w_f32_nk, N, bias, act, out_f8, c_f32, nullptr, stream);
+}
+int mms_dbg_gemm_f8_rows(const float* a_f32, int64_t M, int64_t K, const float* w_f32_nk, int64_t N, const float* bias, int32_t act,
+                         int32_t out_f8, float* c_f32, const mms_rows_spec* rows, void* stream) {
+    if (!a_f32 || !w_f32_nk || !c_f32 || M <= 0 || M > (1 << 24) || N % 256 || K % 128) { g_err = "mms_dbg_gemm_f8: bad argument (N % 256, K % 128)"; return MMS_ERR_ARG; }
+    // rows: the caller's pre-filled physical image with a row map, a live count, a row stride and (fp32) the head-major layout; checked before anything is launched
+    const int32_t ident[3] = {0, 0, 0};
+    int64_t n_out = M * N;
+    if (rows) {
+        if (out_f8 && (rows->out_kind != 0 || rows->ldo % 32)) { g_err = "mms_dbg_gemm_f8: e4m3 output is row-major, ldo % 32 == 0"; return MMS_ERR_ARG; }
+        n_out = dbg_out_elems(rows->out_kind, M, N, rows->ldo, rows->c_rows, rows->cmap, rows->hm_rows, rows->hm_col0, rows->hm_blocks);
+        if (n_out < 0 || rows->out_kind == 1) { g_err = "mms_dbg_gemm_f8: an output row lies outside the image (or bad output fields)"; return MMS_ERR_ARG; }
+    }
     hipStream_t st = (hipStream_t)stream;
     const int64_t Mp = (M + 255) / 256 * 256;
-    unsigned char *a8 = nullptr, *w8 = nullptr, *c8 = nullptr;
-    unsigned* ws4 = nullptr;
-    DBG_TRY(hipMalloc((void**)&a8, (size_t)Mp * K));
+    DbgPool pool;
+    unsigned char* a8 = (unsigned char*)pool.get((size_t)Mp * K);
+    unsigned char* w8 = (unsigned char*)pool.get((size_t)N * K);
+    unsigned* ws4 = (unsigned*)pool.get((size_t)N);
+    unsigned char* c8 = out_f8 ? (unsigned char*)pool.get((size_t)n_out) : nullptr;
+    int* live = (int*)pool.get(16);
+    if (!a8 || !w8 || !ws4 || !live || (out_f8 && !c8)) return dbg_fail("mms_dbg_gemm_f8: hipMalloc");
     DBG_TRY(hipMemsetAsync(a8, 0, (size_t)Mp * K, st));
-    DBG_TRY(hipMalloc((void**)&w8, (size_t)N * K));
-    DBG_TRY(hipMalloc((void**)&ws4, (size_t)N));
     launch_f32_to_f8(a_f32, a8, M * K, st);
     launch_quant_rows_f8(w_f32_nk, w8, nullptr, ws4, (int)N, (int)K, st);
     GemmParams p{};
-    p.a8 = a8; p.lda = (int)K; p.amap = RowMap{0, 0, 0}; p.cmap = RowMap{0, 0, 0}; p.rmap = RowMap{0, 0, 0};
+    p.a8 = a8; p.lda = (int)K; p.amap = RowMap{0, 0, 0}; p.cmap = dbg_rowmap_dev(rows ? rows->cmap : ident); p.rmap = RowMap{0, 0, 0};
     p.w8 = w8; p.w8_scale4 = ws4; p.bias = bias; p.M = (int)M; p.N = (int)N; p.K = (int)K; p.act = act;
+    const int ldo = rows ? rows->ldo : (int)N;
+    if (rows && rows->m_live >= 0) {
+        const int host_live = rows->m_live;
+        DBG_TRY(hipMemcpyAsync(live, &host_live, 4, hipMemcpyHostToDevice, st));
+        DBG_TRY(hipStreamSynchronize(st));      // host_live leaves scope
+        p.m_dev = live;
+    }
     if (out_f8) {
-        DBG_TRY(hipMalloc((void**)&c8, (size_t)M * N));
-        p.out_kind = OUT_F8; p.c_f8 = c8; p.ldf8 = (int)N;
-    } else { p.out_kind = OUT_F32; p.c_f32 = c_f32; p.ldc = (int)N; }
-    if (!launch_gemm_mx8(p, st)) { g_err = "mms_dbg_gemm_f8: shape not supported"; return MMS_ERR_ARG; }
-    if (out_f8) launch_f8_to_f32(c8, c_f32, M * N, st);
+        if (rows) launch_f32_to_f8(c_f32, c8, n_out, st);      // the pre-filled image as bytes
+        p.out_kind = OUT_F8; p.c_f8 = c8; p.ldf8 = ldo;
+    } else {
+        p.out_kind = OUT_F32; p.c_f32 = c_f32; p.ldc = ldo;
+        if (rows && rows->out_kind == 2) { p.hm_rows = rows->hm_rows; p.hm_col0 = rows->hm_col0; }
+    }
+    const bool taken = launch_gemm_mx8(p, st);
+    if (taken && out_f8) launch_f8_to_f32(c8, c_f32, n_out, st);
     DBG_TRY(hipStreamSynchronize(st));
     DBG_TRY(hipGetLastError());
-    (void)hipFree(a8); (void)hipFree(w8); (void)hipFree(ws4); (void)hipFree(c8);
+    if (!taken) { g_err = "mms_dbg_gemm_f8: shape not supported"; return MMS_ERR_ARG; }
     return MMS_OK;
 }
 
@@ -2504,35 +2570,50 @@ int mms_dbg_gemm_ln(const float* a_f32, int64_t M, int64_t K, const float* w_f32
 // -- the kernel pair proj_ln() launches for calls of a few hundred pairs
 int mms_dbg_proj_ln_splitk(const float* a_f32, int64_t M, int64_t K, const float* w_f32_nk, const float* bias, const float* resid_f32,
                            const float* gamma, const float* beta, int32_t splits, float* c_f32, void* stream) {
+    return mms_dbg_proj_ln_splitk_rows(a_f32, M, K, w_f32_nk, bias, resid_f32, gamma, beta, splits, c_f32, nullptr, nullptr, nullptr, stream);
+}
+int mms_dbg_proj_ln_splitk_rows(const float* a_f32, int64_t M, int64_t K, const float* w_f32_nk, const float* bias, const float* resid_f32,
+                                const float* gamma, const float* beta, int32_t splits, float* c_f32, const mms_rows_spec* rows, const int32_t* a_index,
+                                const int32_t* r_index, void* stream) {
     const int64_t N = H;
     const bool skinny_parts = splits < 0;      // negative: the partials come from gemm_skinny.hip (K slices dealt to workgroups; M <= 512) instead of the tile engine
     if (skinny_parts) splits = -splits;
-    if (!a_f32 || !w_f32_nk || !resid_f32 || !gamma || !beta || !c_f32 || M <= 0 || splits == 0 || K % (64 * (splits < 0 ? -splits : splits))) { g_err = "mms_dbg_proj_ln_splitk: bad argument"; return MMS_ERR_ARG; }
+    if (!a_f32 || !w_f32_nk || !resid_f32 || !gamma || !beta || !c_f32 || M <= 0 || M > (1 << 24) || splits == 0 || K % (64 * (splits < 0 ? -splits : splits))) { g_err = "mms_dbg_proj_ln_splitk_rows: bad argument"; return MMS_ERR_ARG; }
+    // rows: A [a_rows][lda] through amap / a_index, the residual [r_rows][768] through rmap / r_index -- every row of r < M inside its buffer, or nothing is launched
+    const int32_t ident[3] = {0, 0, 0};
+    const int64_t a_rows = rows ? rows->a_rows : M, lda = rows ? rows->lda : K, r_rows = rows ? rows->r_rows : M;
+    if ((!rows && (a_index || r_index)) || lda < K || lda % 32 || !dbg_rows_inside(rows ? rows->amap : ident, a_index, M, a_rows) ||
+        !dbg_rows_inside(rows ? rows->rmap : ident, r_index, M, r_rows)) { g_err = "mms_dbg_proj_ln_splitk_rows: a row lies outside its buffer (or bad lda)"; return MMS_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
-    bf16 *ap = nullptr, *wp = nullptr, *rp = nullptr, *cp = nullptr;
-    float* parts = nullptr;
-    DBG_TRY(hipMalloc((void**)&ap, (size_t)M * K * 4)); DBG_TRY(hipMalloc((void**)&wp, (size_t)N * K * 4));
-    DBG_TRY(hipMalloc((void**)&rp, (size_t)M * N * 4)); DBG_TRY(hipMalloc((void**)&cp, (size_t)M * N * 4));
-    DBG_TRY(hipMalloc((void**)&parts, (size_t)splits * M * N * 4));
-    launch_split_f32(a_f32, ap, ap + MMS_PLANE_LO, M * K, st);
+    DbgPool pool;
+    bf16* ap = (bf16*)pool.get((size_t)a_rows * lda * 4);
+    bf16* wp = (bf16*)pool.get((size_t)N * K * 4);
+    bf16* rp = (bf16*)pool.get((size_t)r_rows * N * 4);
+    bf16* cp = (bf16*)pool.get((size_t)M * N * 4);
+    float* parts = (float*)pool.get((size_t)splits * M * N * 4);
+    if (!ap || !wp || !rp || !cp || !parts) return dbg_fail("mms_dbg_proj_ln_splitk: hipMalloc");
+    launch_split_f32(a_f32, ap, ap + MMS_PLANE_LO, a_rows * lda, st);
     launch_tile_weights(w_f32_nk, wp, wp + N * K, N, K, st);
-    launch_split_f32(resid_f32, rp, rp + MMS_PLANE_LO, M * N, st);
+    launch_split_f32(resid_f32, rp, rp + MMS_PLANE_LO, r_rows * N, st);
     GemmParams p{};
-    p.a_hi = ap; p.a_lo = ap + MMS_PLANE_LO; p.lda = (int)K; p.amap = RowMap{0, 0, 0}; p.cmap = RowMap{0, 0, 0}; p.rmap = RowMap{0, 0, 0};
+    p.a_hi = ap; p.a_lo = ap + MMS_PLANE_LO; p.lda = (int)lda; p.amap = dbg_rowmap_dev(rows ? rows->amap : ident); p.a_index = (const int*)a_index;
+    p.cmap = RowMap{0, 0, 0}; p.rmap = RowMap{0, 0, 0};
     p.w = wp; p.M = (int)M; p.N = (int)N; p.K = (int)K; p.act = ACT_NONE;
     p.out_kind = OUT_F32; p.c_f32 = parts; p.ldc = (int)N;
     p.k_splits = splits; p.c_split_stride = (long long)M * N;
     p.engine = skinny_parts && splits > 1 ? ENG_SKINNY_PARTS : ENG_TILE;
     if (splits == 1) p.bias = bias;
-    launch_gemm(p, 2, st);
+    const bool taken = launch_gemm(p, 2, st);
     LnResid r;
-    r.hi = rp; r.lo = rp + MMS_PLANE_LO; r.ld = (int)N;
+    r.hi = rp; r.lo = rp + MMS_PLANE_LO; r.ld = (int)N; r.rmap = dbg_rowmap_dev(rows ? rows->rmap : ident); r.r_index = (const int*)r_index;
     if (splits > 1) { r.nparts = splits; r.part_stride = p.c_split_stride; r.bias = bias; }
-    launch_ln_to_planes(parts, (int)N, gamma, beta, cp, cp + MMS_PLANE_LO, (int)N, (int)M, st, nullptr, r);
-    launch_planes_to_f32(cp, cp + MMS_PLANE_LO, c_f32, M * N, st);
+    if (taken) {
+        launch_ln_to_planes(parts, (int)N, gamma, beta, cp, cp + MMS_PLANE_LO, (int)N, (int)M, st, nullptr, r);
+        launch_planes_to_f32(cp, cp + MMS_PLANE_LO, c_f32, M * N, st);
+    }
     DBG_TRY(hipStreamSynchronize(st));
     DBG_TRY(hipGetLastError());
-    for (void* q : {(void*)ap, (void*)wp, (void*)rp, (void*)cp, (void*)parts}) (void)hipFree(q);
+    if (!taken) { g_err = "mms_dbg_proj_ln_splitk_rows: no engine takes this shape"; return MMS_ERR_ARG; }
     return MMS_OK;
 }
 
@@ -2774,17 +2855,6 @@ int mms_dbg_layernorm(const float* x, const float* gamma, const float* beta, int
 }
 
 // ---- hooks of the ragged attention, plan, de-duplication and row kernels: the launch forms the forwards use (att_block, last_block_cls, the pack plans) ----
-// device buffers of one hook call, freed on every way out
-struct DbgPool {
-    std::vector<void*> p;
-    ~DbgPool() { for (void* q : p) (void)hipFree(q); }
-    void* get(size_t bytes) {
-        void* q = nullptr;
-        if (hipMalloc(&q, bytes ? bytes : 4) != hipSuccess) return nullptr;
-        p.push_back(q);
-        return q;
-    }
-};
 // per-pair rows of a ragged stream, checked on the host before a kernel reads through them: 1 <= cnt <= S, [off, off + cnt) inside the stream
 static bool dbg_pairs_ok(const int32_t* off_dev, const int32_t* cnt_dev, int64_t B, int S, int64_t rows) {
     std::vector<int32_t> off((size_t)B), cnt((size_t)B);
@@ -2924,9 +2994,14 @@ int mms_dbg_gemm_ex(const float* a_f32, int64_t M, int64_t K, const float* w_f32
 
 int mms_dbg_layernorm_ex(const float* x, const float* gamma, const float* beta, int64_t M, const float* resid_f32, int64_t resid_rows, const int32_t* r_index,
                          int64_t m_live, int32_t flags, float* out_f32, float* out_f8, void* stream) {
+    return mms_dbg_layernorm_rows(x, gamma, beta, M, resid_f32, resid_rows, r_index, m_live, flags, out_f32, out_f8, nullptr, stream);
+}
+int mms_dbg_layernorm_rows(const float* x, const float* gamma, const float* beta, int64_t M, const float* resid_f32, int64_t resid_rows, const int32_t* r_index,
+                           int64_t m_live, int32_t flags, float* out_f32, float* out_f8, const int32_t* rmap, void* stream) {
     const bool f8 = flags & 2;
     if (!x || !gamma || !beta || !out_f32 || M <= 0 || M > (1 << 24) || (flags & ~7) || (f8 && !out_f8) || (resid_f32 && resid_rows <= 0) || (r_index && !resid_f32) ||
-        (resid_f32 && !r_index && resid_rows < M)) { g_err = "mms_dbg_layernorm_ex: bad argument"; return MMS_ERR_ARG; }
+        (rmap && (!resid_f32 || r_index)) || (resid_f32 && !r_index && !rmap && resid_rows < M)) { g_err = "mms_dbg_layernorm_ex: bad argument"; return MMS_ERR_ARG; }
+    if (rmap && !dbg_rows_inside(rmap, nullptr, M, resid_rows)) { g_err = "mms_dbg_layernorm_ex: rmap leaves the residual"; return MMS_ERR_ARG; }
     if (r_index) {
         std::vector<int32_t> ri((size_t)M);
         DBG_TRY(hipMemcpy(ri.data(), r_index, (size_t)M * 4, hipMemcpyDeviceToHost));
@@ -2948,6 +3023,7 @@ int mms_dbg_layernorm_ex(const float* x, const float* gamma, const float* beta, 
     if (resid_f32) {
         launch_split_f32(resid_f32, rp, rp + MMS_PLANE_LO, resid_rows * H, st);
         r.hi = rp; r.lo = rp + MMS_PLANE_LO; r.ld = H; r.r_index = (const int*)r_index;
+        if (rmap) r.rmap = dbg_rowmap_dev(rmap);
     }
     r.reverse = flags & 1;
     if (f8) r.o_f8 = o8;
@@ -2973,6 +3049,90 @@ int mms_dbg_convert(int32_t kind, const void* in, void* out, int64_t n, void* st
         if (kind == 2) launch_planes_to_f32(pl, pl + MMS_PLANE_LO, (float*)out, n, st);
         else launch_planes_to_f8(pl, pl + MMS_PLANE_LO, (unsigned char*)out, n, st);
     }
+    DBG_TRY(hipStreamSynchronize(st));
+    DBG_TRY(hipGetLastError());
+    return MMS_OK;
+}
+
+// the launcher of ONE named engine, without the fall-backs of gemm_dispatch.hip's run_engine: what the engine refuses comes back as false
+static bool dbg_launch_named(const GemmParams& p, int nsplit, hipStream_t st) {
+    switch ((Engine)p.engine) {
+        case ENG_TILE_128: return launch_gemm_tile(p, nsplit, ENG_TILE_128, st);
+        case ENG_TILE_DMA: case ENG_TILE: case ENG_TILE_256: return nsplit != 3 && launch_gemm_tile(p, nsplit, (Engine)p.engine, st);      // (three passes: the 128 x 128 tile only)
+        case ENG_PP: return launch_gemm_pp(p, nsplit, 0, st);
+        case ENG_PP_PERSIST: return launch_gemm_pp(p, nsplit, 0, st, true);
+        case ENG_PPW: return nsplit == 3 && launch_gemm_ppw(p, st);
+        case ENG_SKINNY: return launch_gemm_skinny(p, nsplit, st);
+        case ENG_SKINNY_K4: case ENG_SKINNY_K8: { GemmParams q = p; q.wave_k_slices = p.engine == ENG_SKINNY_K4 ? 4 : 8; return launch_gemm_skinny(q, nsplit, st); }
+        default: return false;
+    }
+}
+
+int mms_dbg_gemm_rows(const mms_rows_spec* s, const float* a_f32, const int32_t* a_index, const float* w_f32_nk, const float* bias, const float* resid_f32,
+                      const int32_t* r_index, float* c_f32, void* stream) {
+    if (!s || !a_f32 || !w_f32_nk || !c_f32 || s->M <= 0 || s->M > (1 << 24) || s->N <= 0 || s->N % 128 || s->K <= 0 || s->K % 64 || s->nsplit < 1 || s->nsplit > 3 ||
+        s->act < ACT_NONE || s->act > ACT_TANH || (s->reverse & ~1) || s->a_rows <= 0 || s->lda < s->K || s->lda % 32 || (r_index && !resid_f32)) {
+        g_err = "mms_dbg_gemm_rows: bad argument"; return MMS_ERR_ARG;
+    }
+    const int64_t M = s->M, N = s->N, K = s->K;
+    // every row (and head-major block) a logical row r < M can address, BEFORE anything is launched: a slip in a caller's spec ends here, not in a fault
+    if (!dbg_rows_inside(s->amap, a_index, M, s->a_rows)) { g_err = "mms_dbg_gemm_rows: an A row lies outside a_f32"; return MMS_ERR_ARG; }
+    if (resid_f32 && !dbg_rows_inside(s->rmap, r_index, M, s->r_rows)) { g_err = "mms_dbg_gemm_rows: a residual row lies outside resid_f32"; return MMS_ERR_ARG; }
+    const int64_t n_out = dbg_out_elems(s->out_kind, M, N, s->ldo, s->c_rows, s->cmap, s->hm_rows, s->hm_col0, s->hm_blocks);
+    if (n_out < 0) { g_err = "mms_dbg_gemm_rows: an output row lies outside c_f32 (or bad output fields)"; return MMS_ERR_ARG; }
+    hipStream_t st = (hipStream_t)stream;
+    DbgPool pool;
+    bf16* ap = (bf16*)pool.get((size_t)s->a_rows * s->lda * 4);
+    bf16* wp = (bf16*)pool.get((size_t)N * K * 4);
+    bf16* rp = resid_f32 ? (bf16*)pool.get((size_t)s->r_rows * N * 4) : nullptr;
+    bf16* cp = s->out_kind == 1 ? (bf16*)pool.get((size_t)n_out * 4) : nullptr;
+    int* live = (int*)pool.get(16);
+    if (!ap || !wp || !live || (resid_f32 && !rp) || (s->out_kind == 1 && !cp)) return dbg_fail("mms_dbg_gemm_rows: hipMalloc");
+    DBG_TRY(hipMemcpyAsync(live, &s->m_live, 4, hipMemcpyHostToDevice, st));
+    launch_split_f32(a_f32, ap, ap + MMS_PLANE_LO, (int64_t)s->a_rows * s->lda, st);
+    launch_tile_weights(w_f32_nk, wp, wp + N * K, N, K, st);
+    GemmParams p{};
+    p.a_hi = ap; p.a_lo = ap + MMS_PLANE_LO; p.lda = s->lda; p.amap = dbg_rowmap_dev(s->amap); p.a_index = (const int*)a_index;
+    p.w = wp; p.w_lo = wp + N * K; p.bias = bias; p.M = (int)M; p.N = (int)N; p.K = (int)K; p.act = s->act;
+    p.cmap = dbg_rowmap_dev(s->cmap);
+    p.engine = s->engine; p.reverse = s->reverse;
+    if (s->m_live >= 0) p.m_dev = live;
+    if (resid_f32) {
+        launch_split_f32(resid_f32, rp, rp + MMS_PLANE_LO, (int64_t)s->r_rows * N, st);
+        p.r_hi = rp; p.r_lo = rp + MMS_PLANE_LO; p.ldr = (int)N; p.rmap = dbg_rowmap_dev(s->rmap); p.r_index = (const int*)r_index;
+    }
+    if (s->out_kind == 1) {
+        launch_split_f32(c_f32, cp, cp + MMS_PLANE_LO, n_out, st);      // the caller's pre-filled image (a value with an exact hi / lo split comes back as it went in)
+        p.out_kind = OUT_PLANES; p.c_hi = cp; p.c_lo = cp + MMS_PLANE_LO; p.ldp = s->ldo;
+    } else {
+        p.out_kind = OUT_F32; p.c_f32 = c_f32; p.ldc = s->ldo;
+        if (s->out_kind == 2) { p.hm_rows = s->hm_rows; p.hm_col0 = s->hm_col0; }
+    }
+    const bool taken = dbg_launch_named(p, s->nsplit, st);
+    if (taken && s->out_kind == 1) launch_planes_to_f32(cp, cp + MMS_PLANE_LO, c_f32, n_out, st);      // the WHOLE physical buffer
+    DBG_TRY(hipStreamSynchronize(st));
+    DBG_TRY(hipGetLastError());
+    if (!taken) { g_err = "mms_dbg_gemm_rows: the engine refuses this launch"; return MMS_ERR_ARG; }
+    return MMS_OK;
+}
+
+int mms_dbg_splitk_reduce(const float* parts, int32_t S, int64_t M, int64_t N, const float* bias, int32_t act, int64_t m_live, int32_t out_kind, int32_t ldo,
+                          int64_t c_rows, int32_t hm_rows, int32_t hm_col0, int32_t hm_blocks, float* c_f32, void* stream) {
+    if (!parts || !c_f32 || S < 1 || S > 64 || M <= 0 || M > (1 << 24) || N <= 0 || N % 4 || act < ACT_NONE || act > ACT_TANH) { g_err = "mms_dbg_splitk_reduce: bad argument"; return MMS_ERR_ARG; }
+    const int32_t ident[3] = {0, 0, 0};
+    const int64_t n_out = dbg_out_elems(out_kind, M, N, ldo, c_rows, ident, hm_rows, hm_col0, hm_blocks);      // the kernel writes row r to row r: M rows must fit
+    if (n_out < 0) { g_err = "mms_dbg_splitk_reduce: an output row lies outside c_f32 (or bad output fields)"; return MMS_ERR_ARG; }
+    hipStream_t st = (hipStream_t)stream;
+    DbgPool pool;
+    bf16* cp = out_kind == 1 ? (bf16*)pool.get((size_t)n_out * 4) : nullptr;
+    int* live = (int*)pool.get(16);
+    if (!live || (out_kind == 1 && !cp)) return dbg_fail("mms_dbg_splitk_reduce: hipMalloc");
+    const int host_live = (int)m_live;
+    DBG_TRY(hipMemcpyAsync(live, &host_live, 4, hipMemcpyHostToDevice, st));
+    if (cp) launch_split_f32(c_f32, cp, cp + MMS_PLANE_LO, n_out, st);
+    launch_splitk_reduce(parts, S, M * N, (int)M, (int)N, m_live >= 0 ? live : nullptr, bias, act, cp ? nullptr : c_f32, ldo, out_kind == 2 ? hm_rows : 0, hm_col0,
+                         cp, cp ? cp + MMS_PLANE_LO : nullptr, ldo, st);
+    if (cp) launch_planes_to_f32(cp, cp + MMS_PLANE_LO, c_f32, n_out, st);
     DBG_TRY(hipStreamSynchronize(st));
     DBG_TRY(hipGetLastError());
     return MMS_OK;

@@ -31,6 +31,9 @@ struct GemmParams {
     // quantisation scale, applied to the accumulator before the bias; OUT_F8 stores e4m3 bytes at c_f8[row * ldf8 + col]
     // OUT_F32, head-major (hm_rows > 0): the 64-column group G = (hm_col0 + col) / 64 of row r goes to c_f32[(G * hm_rows + r) * 64 + ...]
     // -- the [Q | K | V] projection laid out as 36 contiguous [rows][64] blocks (12 heads each), which is how the attention kernel reads it
+    // Contract of the head-major store: N % 64 == 0 and hm_col0 % 64 == 0 -- a 64- or 128-wide wave (gemm_pp.hip, gemm_mx.hip) begins a head, a 32-wide one
+    // (gemm_ppw.hip) is the lower or upper half of one, the tile and skinny epilogues place every float4 on its own; hm_rows >= every cmap(r), r < M.  Every
+    // engine honours any such hm_col0 (0 and 768 are what a forward passes; tests/test_gemm_addressing_gpu.py also runs 64)
     int hm_rows, hm_col0;
     int f8;
     const float* col_scale;
@@ -61,6 +64,14 @@ struct GemmParams {
 int device_cu_count();
 // padded row bound from which the persistent ping-pong engines (and the fused LayerNorm epilogue) take a launch (gemm_dispatch.hip)
 int pp_rows();
+// Row addressing, the same in every engine: A row of logical row r = a_index ? a_index[r] : amap(r) (rows r >= M_eff re-read row M_eff - 1: entries of a_index past
+// the live count are never dereferenced), residual row = r_index ? r_index[r] : rmap(r), output row = cmap(r); rows r >= M_eff = min(M, *m_dev) are not written,
+// nor are the columns [N, ldc / ldp) of a row.  What a launcher REFUSES (returns false, nothing launched; tests/test_gemm_addressing_gpu.py asserts those that mms_dbg_gemm_rows reaches):
+//   launch_gemm_skinny / _parts   a residual in the epilogue (r_hi), one-pass launches (nsplit 1), more than 512 rows, fp8; _parts also cmap, bias, activation, head-major, planes
+//   launch_gemm_pp                nsplit 3 (launch_gemm_ppw is the three-pass engine, and that one needs w_lo); N % 256
+//   launch_gemm_pp_ln             every row map and gather (identity only)
+//   launch_gemm_mx8 / _mx         amap, a_index (A8 rows are read by row number, allocated up to a multiple of 256) and a residual; cmap, m_dev, ldc / ldf8, head-major are honoured
+//   launch_gemm_tile              ENG_TILE / _DMA / _256 at N % 256; split-K launches with bias, residual, activation, planes or head-major output
 bool launch_gemm(const GemmParams& p, int nsplit, hipStream_t st);      // false: no engine took the shape, nothing was launched
 bool launch_gemm_tile(const GemmParams& p, int nsplit, Engine tile, hipStream_t st);  // gemm_tile.hip: ENG_TILE_128 / ENG_TILE_DMA / ENG_TILE / ENG_TILE_256
 bool launch_gemm_skinny_parts(const GemmParams& p, int nsplit, hipStream_t st);        // ... with the K slices dealt to workgroups: k_splits fp32 partials, c_split_stride apart (ENG_SKINNY_PARTS; the LayerNorm kernel sums them)

@@ -58,6 +58,13 @@ class EnsembleBatch(C.Structure):
                 ("lx_input_ids", C.c_void_p), ("lx_input_mask", C.c_void_p)]
 
 
+class RowsSpec(C.Structure):
+    """mms_rows_spec of include/mmscore.h: the addressing fields of one GEMM launch (mms_dbg_gemm_rows; optional on mms_dbg_gemm_f8 / mms_dbg_proj_ln_splitk)."""
+    _fields_ = [(n, C.c_int32) for n in ("M", "N", "K", "nsplit", "engine", "act", "reverse", "m_live", "a_rows", "lda")] + [("amap", C.c_int32 * 3), ("r_rows", C.c_int32),
+               ("rmap", C.c_int32 * 3), ("out_kind", C.c_int32), ("ldo", C.c_int32), ("c_rows", C.c_int32), ("cmap", C.c_int32 * 3), ("hm_rows", C.c_int32),
+               ("hm_col0", C.c_int32), ("hm_blocks", C.c_int32)]
+
+
 ABI_VERSION = 10    # include/mmscore.h MMS_ABI_VERSION
 
 # enum Engine of csrc/regimes.h (mms_dbg_gemm / mms_dbg_gemm_bench name ONE GEMM engine per call; tests/test_abi.py holds the two lists together)
@@ -68,7 +75,7 @@ EXPORTS = ("mms_version", "mms_global_error", "mms_create", "mms_destroy", "mms_
            "mms_finalize", "mms_score_zk", "mms_score_lds", "mms_score_lxmert", "mms_score_ensemble", "mms_gemm_timing", "mms_gemm_timing_class",
            "mms_debug_read_x", "mms_dbg_gemm", "mms_dbg_gemm_f8", "mms_dbg_gemm_ln", "mms_dbg_proj_ln_splitk", "mms_dbg_attention", "mms_dbg_qkv_attn", "mms_dbg_layernorm",
            "mms_dbg_gemm_bench", "mms_dbg_counter", "mms_fused_timing", "mms_side_lane_flops", "mms_decode_feats_b64",
-           "mms_dbg_attention_ex", "mms_dbg_pack_plan", "mms_dbg_dedup", "mms_dbg_layernorm_ex", "mms_dbg_gemm_ex", "mms_dbg_convert", "mms_rank_workspace_bytes", "mms_rank_submission",
+           "mms_dbg_attention_ex", "mms_dbg_pack_plan", "mms_dbg_dedup", "mms_dbg_layernorm_ex", "mms_dbg_gemm_ex", "mms_dbg_convert", "mms_dbg_gemm_rows", "mms_dbg_splitk_reduce", "mms_dbg_gemm_f8_rows", "mms_dbg_proj_ln_splitk_rows", "mms_dbg_layernorm_rows", "mms_rank_workspace_bytes", "mms_rank_submission",
            "mms_ndcg_workspace_bytes", "mms_key_relevance", "mms_ndcg_at_k", "mms_ndcg_sweep_workspace_bytes", "mms_ndcg_weight_sweep")
 LAB_EXPORTS = ("mms_dbg_gemm_mx", "mms_lab_ln_trace")      # libmmscore_lab.so only
 
@@ -116,10 +123,12 @@ def load(path=None):
     lib.mms_ndcg_sweep_workspace_bytes.restype = i64
     lib.mms_ndcg_weight_sweep.argtypes = [vp, vp, vp, i32, i64, vp, vp, vp, i64, i64, vp, i64, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp]
     lib.mms_dbg_gemm_f8.argtypes = [vp, i64, i64, vp, i64, vp, i32, i32, vp, vp]
+    lib.mms_dbg_gemm_f8_rows.argtypes = [vp, i64, i64, vp, i64, vp, i32, i32, vp, C.POINTER(RowsSpec), vp]
     if hasattr(lib, "mms_dbg_gemm_mx"):      # lab build
         lib.mms_dbg_gemm_mx.argtypes = [vp, i64, i64, vp, i64, vp, i32, i32, vp, vp]
     lib.mms_dbg_gemm_ln.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, i32, vp, C.POINTER(i32), vp]
     lib.mms_dbg_proj_ln_splitk.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, i32, vp, vp]
+    lib.mms_dbg_proj_ln_splitk_rows.argtypes = [vp, i64, i64, vp, vp, vp, vp, vp, i32, vp, C.POINTER(RowsSpec), vp, vp, vp]
     lib.mms_gemm_timing.argtypes = [vp, i32, i32, C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(C.c_double)]
     lib.mms_gemm_timing_class.argtypes = [vp, i32, C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(C.c_double)]
     lib.mms_debug_read_x.argtypes = [vp, vp, i64, vp]
@@ -131,8 +140,11 @@ def load(path=None):
     lib.mms_dbg_pack_plan.argtypes = [i32, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mms_dbg_dedup.argtypes = [i32, vp, vp, i32, i64, C.POINTER(i32), vp, vp, vp, vp, vp]
     lib.mms_dbg_layernorm_ex.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, i32, vp, vp, vp]
+    lib.mms_dbg_layernorm_rows.argtypes = [vp, vp, vp, i64, vp, i64, vp, i64, i32, vp, vp, C.POINTER(i32), vp]
     lib.mms_dbg_gemm_ex.argtypes = [vp, i64, i64, vp, i64, vp, i32, i32, i32, i64, i32, vp, vp]
     lib.mms_dbg_convert.argtypes = [i32, vp, vp, i64, vp]
+    lib.mms_dbg_gemm_rows.argtypes = [C.POINTER(RowsSpec), vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mms_dbg_splitk_reduce.argtypes = [vp, i32, i64, i64, vp, i32, i64, i32, i32, i64, i32, i32, i32, vp, vp]
     lib.mms_dbg_counter.argtypes = [vp, i32]
     lib.mms_fused_timing.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(i64), C.POINTER(C.c_double)]
     lib.mms_side_lane_flops.argtypes = [vp, C.POINTER(C.c_double)]

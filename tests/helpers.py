@@ -181,3 +181,71 @@ def act_ref(x, act):
     if act == lib.ACT_TANH:
         return np.tanh(x)
     return x
+
+
+# ---- numpy statements of the GEMM addressing fields (GemmParams amap / a_index / rmap / r_index / cmap / ldc / ldp / hm_rows / hm_col0 / m_dev),
+# written from their definitions in csrc/common.h and csrc/kernels.h, not from an engine; tests/test_gemm_rows_spec.py pins them on the CPU ----
+def rowmap(r, grp, stride, off):
+    """RowMap of csrc/common.h: logical row r -> physical row (r // grp) * stride + off + r % grp; grp == 0 is the identity."""
+    r = np.asarray(r, np.int64)
+    return r.copy() if grp == 0 else (r // grp) * stride + off + r % grp
+
+
+def head_major_index(row, col, hm_rows, hm_col0):
+    """Flat index of (row, col) in the head-major fp32 layout [blocks][hm_rows][64]: column hm_col0 + col lies in block (hm_col0 + col) // 64."""
+    c = hm_col0 + np.asarray(col, np.int64)
+    return ((c // 64) * hm_rows + np.asarray(row, np.int64)) * 64 + c % 64
+
+
+def rows_spec(M, N, K, engine, **kw):
+    """The fields of mms_rows_spec (include/mmscore.h) as a dict, dense defaults: identity maps, lda == K, plain fp32 [M][N] out, no live count."""
+    d = dict(M=M, N=N, K=K, nsplit=2, engine=engine, act=0, reverse=0, m_live=-1, a_rows=M, lda=K, amap=(0, 0, 0), r_rows=M, rmap=(0, 0, 0), out_kind=0, ldo=N,
+             c_rows=M, cmap=(0, 0, 0), hm_rows=0, hm_col0=0, hm_blocks=0)
+    assert set(kw) <= set(d), set(kw) - set(d)
+    d.update(kw)
+    return d
+
+
+def rows_live(spec):
+    return spec["M"] if spec["m_live"] < 0 else min(spec["M"], spec["m_live"])
+
+
+def rows_image_shape(spec):
+    """Shape of the physical output a spec describes: [c_rows][ldo] (fp32 or the fp32 image of split planes) or [hm_blocks][hm_rows][64]."""
+    return (spec["hm_blocks"], spec["hm_rows"], 64) if spec["out_kind"] == 2 else (spec["c_rows"], spec["ldo"])
+
+
+def scatter_rows(values, spec, fill=7.0, dtype=np.float64):
+    """values [>= live][N] by LOGICAL row -> (physical image pre-filled with `fill`, boolean mask of the elements a launch must write): the live rows
+    r < min(M, m_live) through cmap, into columns [0, N) of a row of ldo or into the head-major blocks from hm_col0 // 64 on."""
+    live, N = rows_live(spec), spec["N"]
+    img = np.full(rows_image_shape(spec), fill, dtype)
+    mask = np.zeros(img.shape, bool)
+    orow = rowmap(np.arange(live), *spec["cmap"])
+    assert len(np.unique(orow)) == live, "cmap sends two live rows to one output row"
+    if spec["out_kind"] == 2:
+        idx = head_major_index(orow[:, None], np.arange(N)[None, :], spec["hm_rows"], spec["hm_col0"])
+        assert live == 0 or (idx.min() >= 0 and idx.max() < img.size)
+        img.reshape(-1)[idx] = np.asarray(values)[:live]
+        mask.reshape(-1)[idx] = True
+    else:
+        assert live == 0 or (orow.min() >= 0 and orow.max() < spec["c_rows"])
+        img[orow, :N] = np.asarray(values)[:live]
+        mask[orow, :N] = True
+    return img, mask
+
+
+def gemm_rows_ref(spec, a, w, bias=None, resid=None, a_index=None, r_index=None, fill=7.0):
+    """fp64 statement of ONE GEMM launch with its addressing fields (mms_dbg_gemm_rows): C[cmap(r)] = act(A[a_index[r] or amap(r)] W^T + bias +
+    resid[r_index[r] or rmap(r)]) for the live rows.  a [a_rows][lda], w [N][K], resid [r_rows][N]: the operands as the kernel consumes them.  Returns
+    (expected physical image in fp64, mask of the elements that must be written); everything else keeps `fill`."""
+    live, K = rows_live(spec), spec["K"]
+    r = np.arange(live)
+    arow = np.asarray(a_index, np.int64)[:live] if a_index is not None else rowmap(r, *spec["amap"])
+    v = np.asarray(a, np.float64)[arow, :K] @ np.asarray(w, np.float64).T
+    if bias is not None:
+        v = v + np.asarray(bias, np.float64)
+    if resid is not None:
+        rrow = np.asarray(r_index, np.int64)[:live] if r_index is not None else rowmap(r, *spec["rmap"])
+        v = v + np.asarray(resid, np.float64)[rrow]
+    return scatter_rows(act_ref(v, spec["act"]), spec, fill)

@@ -1,5 +1,7 @@
 """GPU suite, kernel level: the LayerNorm kernel with the fields a forward sets (gathered residual, device-side row count, reversed walk, e4m3
 copy, skip word) against the fp64 LayerNorm, and the fp8 / split-plane conversion kernels against the OCP e4m3 tables of oracle/fp8.py."""
+import ctypes as C
+
 import numpy as np
 import pytest
 import torch
@@ -72,6 +74,42 @@ def test_layernorm_with_gathered_residual_row_count_and_direction():
     assert np.abs(plain - _ln_ref(x, g, b)).max() < 5e-5
     skipped, s8 = _ln(x, g, b, resid, r_index, -1, SKIP | F8)        # the producing GEMM already normalised: nothing is written
     assert np.all(skipped == 0.0) and np.all(s8 == 0.0)
+
+
+def _ln_rows(x, g, b, resid, rmap, m_live, flags, expect=0):
+    """mms_dbg_layernorm_rows: the LayerNorm kernel with LnResid::rmap = {grp, stride, off}"""
+    l = lib.load()
+    M = x.shape[0]
+    out = torch.full((M, 768), 7.0, device="cuda", dtype=torch.float32)
+    hold = [_dev(x), _dev(g), _dev(b), _dev(resid)]
+    rc = l.mms_dbg_layernorm_rows(hold[0].data_ptr(), hold[1].data_ptr(), hold[2].data_ptr(), M, hold[3].data_ptr(), resid.shape[0], None, m_live, flags,
+                                  out.data_ptr(), None, (C.c_int32 * 3)(*rmap), None)
+    assert rc == expect, l.mms_global_error()
+    return out.cpu().numpy()
+
+
+def test_layernorm_with_a_row_mapped_residual():
+    """LnResid::rmap = {1, 30, 0}: row r adds residual row 30 r (the CLS-only last layer's residual through the dense token stream).  Every residual row the
+    map does not address holds NaN; same reference and bound as the r_index case, bit-identical to the r_index launch that names the same rows, with and
+    without a live count and reversed; a map that leaves the residual is refused on the host."""
+    M, x, g, b = _ln_inputs()
+    rmap = (1, 30, 0)
+    rows = helpers.rowmap(np.arange(M), *rmap)
+    dense = weights.normal("rk/resid_map", (M, 768), 3, 1.5)
+    resid = np.full((M * rmap[1], 768), np.nan, np.float32)
+    resid[rows] = dense
+    ref = _ln_ref(x.astype(np.float64) + _split_join(dense), g, b)
+    got = _ln_rows(x, g, b, resid, rmap, -1, 0)
+    err = np.abs(got - ref).max()
+    print("LayerNorm + row-mapped residual: worst error %.2e (bound 5e-5)" % err)
+    assert err < 5e-5
+    assert np.array_equal(got, _ln(x, g, b, resid, rows, -1, 0)[0])
+    live = M - 3
+    for flags in (0, REV):
+        part = _ln_rows(x, g, b, resid, rmap, live, flags)
+        assert np.array_equal(part[:live], got[:live]) and np.all(part[live:] == 0.0), flags
+    short = _ln_rows(x, g, b, resid[:-rmap[1]], rmap, -1, 0, expect=1)      # the last row's residual lies outside: MMS_ERR_ARG before any launch
+    assert np.all(short == 7.0)
 
 
 def test_layernorm_fp8_copy():
