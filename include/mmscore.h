@@ -174,11 +174,11 @@ typedef struct mms_ensemble_batch {
 /* ABI revision of the structs and entry points declared in this header.  It changes whenever a struct gains a field or an entry
  * point changes its signature (r1: 1; r2 added mms_config.fuse_layernorm, mms_zk_batch.label_ids, mms_lxmert_batch.label_ids / x_norm
  * without bumping it; r3: 3, then 4 with mms_config.fuse_attention; r4: 5 -- mms_dbg_gemm takes the engine per call,
- * the process-global mms_set_gemm_variant and the lab engines' hooks left the product library, fuse_layernorm became a mask; r5: 6 -- mms_dbg_qkv_attn and mms_side_lane_flops added; r7: 7 -- mms_decode_feats_b64 added; r8: 8 -- mms_rank_workspace_bytes and mms_rank_submission added; r9: 9 -- mms_ndcg_workspace_bytes, mms_key_relevance and mms_ndcg_at_k added; r10: 10 -- mms_ndcg_sweep_workspace_bytes and mms_ndcg_weight_sweep added).  A caller built against another revision would make the library read past its structs, so compare
+ * the process-global mms_set_gemm_variant and the lab engines' hooks left the product library, fuse_layernorm became a mask; r5: 6 -- mms_dbg_qkv_attn and mms_side_lane_flops added; r7: 7 -- mms_decode_feats_b64 added; r8: 8 -- mms_rank_workspace_bytes and mms_rank_submission added; r9: 9 -- mms_ndcg_workspace_bytes, mms_key_relevance and mms_ndcg_at_k added; r10: 10 -- mms_ndcg_sweep_workspace_bytes and mms_ndcg_weight_sweep added; r11: 11 -- mms_filter_sweep_workspace_bytes and mms_filter_sweep added).  A caller built against another revision would make the library read past its structs, so compare
  * BEFORE the first mms_create:  if (mms_version() != MMS_ABI_VERSION) abort();   (lib.py's load() does) */
-#define MMS_ABI_VERSION 10
+#define MMS_ABI_VERSION 11
 int mms_version(void);
-const char* mms_global_error(void);              /* message of the last failing mms_create / mms_decode_feats_b64 / mms_rank_submission / mms_key_relevance / mms_ndcg_at_k / mms_ndcg_weight_sweep */
+const char* mms_global_error(void);              /* message of the last failing mms_create / mms_decode_feats_b64 / mms_rank_submission / mms_key_relevance / mms_ndcg_at_k / mms_ndcg_weight_sweep / mms_filter_sweep */
 
 int mms_create(const mms_config* cfg, mms_handle** out);
 void mms_destroy(mms_handle* h);
@@ -368,6 +368,55 @@ int mms_ndcg_weight_sweep(const int64_t* query_id, const int64_t* product_id, co
                           const double* bin_value /* device [(k+1)<<k] or NULL */, int64_t n_key_queries_total /* divisor of value_out */,
                           void* workspace, int64_t workspace_bytes, int64_t* hist_out /* [n_weights][(k+1)<<k], zeroed by the call */,
                           double* value_out /* [n_weights] or NULL; needs bin_value */, int32_t* status /* [4] as mms_ndcg_at_k */, void* stream);
+
+/* Fitting the uniqueness filter on the valid set: the nDCG@k histogram -- and, optionally, the value and the per-query codes -- of the SUBMISSION
+ * rows (what mms_rank_submission writes: code/main.py:76-104) for EVERY (gap, tie) pair of a grid in one call.  Rows, answer key, allow_missing and
+ * status words are those of mms_ndcg_at_k; the score is given as fp32 OR fp64 (exactly one of score_f32 / score_f64 is non-NULL); filters is a
+ * device fp64 array [n_filters][2] with rows (gap, tie).  k in 1..MMS_FILTER_MAX_K: a submission row holds five products.
+ *   ARITHMETIC CONTRACT, decision for decision that of mms_rank_submission and of ensemble.submission_rows, in IEEE double on the scores widened
+ *   exactly, -0.0 == +0.0:
+ *     per product, over ALL rows -- also rows of queries outside the key:  d = best - second, second = best when two rows share the maximum;
+ *     keep_product = (rows of the product < 2) or not (d < gap);   survive(row) = keep_product and |score - best| < tie;
+ *     per key query: >= 5 survivors -> its best survivors; 1..4 survivors -> its best rows overall; order: score descending, then row ascending.
+ *   A NaN or +-inf gap / tie is no error: the two comparisons decide as they do in Python ((-inf, +inf) keeps every product and every row, so the
+ *   output row is the unfiltered top-5 and the histogram is that of mms_ndcg_at_k).
+ *   code_out[g][i] (optional), for filter g and key query i:  -1 when the query has no rows;  -2 when it has rows but no survivor (main.py writes
+ *   no row for it; it scores 0);  otherwise mask | ideal << 8 with bit j of mask set when the j-th product of its output row is in its truth list
+ *   (j < min(k, products written)) and ideal = min(distinct products of the truth list, k).  hist_out[g][ideal << k | mask] += 1 over the codes >= 0
+ *   ((k + 1) << k int64 bins per filter, zeroed by the call) -- ndcg.submission_codes / ndcg.filter_sweep_host on the host.
+ *       value_out[g] = (sum over ALL bins b in bin order of double(hist_out[g][b]) * bin_value[b]) / n_key_queries_total
+ *   each product, each sum and the division rounded on its own, as in mms_ndcg_weight_sweep: ndcg.ndcg_from_hist(hist_out[g], k,
+ *   n_key_queries_total) bit for bit.  The divisor is the caller's (the whole key's length): a dropped or missing query costs its share, as a
+ *   grader of the submission file charges it.  value_out may be NULL; given, it needs bin_value and n_key_queries_total >= 1.
+ *   The filter is global over the rows: histograms of query shards do NOT add up to the whole table's (a product's second best may sit in another
+ *   shard).  Run the call on the gathered table.
+ *   flags (status[2]):  bits 0-3 as mms_ndcg_at_k, but bit 1 covers a non-finite score in ANY row (the product statistics read every row);
+ *           bit 4  a (query, product) pair occurs more than once (the table semantics "last score wins" stay with the host form, as in
+ *                  mms_rank_submission)
+ *   With a non-zero flag word (other than bit 0 under allow_missing, which is never set then) the outputs are unspecified, but nothing is written
+ *   outside them or outside the workspace.
+ *   workspace: device memory, 256-byte aligned, at least mms_filter_sweep_workspace_bytes(n, n_key_queries, n_key_products) bytes.
+ * Everything but the two comparisons against (gap, tie) runs once per call: the score-independent stages of mms_ndcg_at_k, the product statistics
+ * of mms_rank_submission, the records (score image, row, relevance, d, |score - best|) and the unfiltered top-k; then a wavefront takes a key query
+ * and a tile of 64 filters, a lane owning one filter (csrc/filter_sweep.hip).  Integer atomics only: equal inputs give bit-equal outputs.  No kernel
+ * waits on another workgroup.  ONLY ENQUEUES on `stream` (fills and at most fifteen kernels): no allocation, no synchronisation, no device -> host
+ * read.  Handle-free.
+ * Returns MMS_ERR_ARG (message in mms_global_error naming the function, nothing launched) for a count that is negative or over its cap (those of
+ * mms_ndcg_at_k; n_filters <= MMS_FILTER_MAX), k outside 1..MMS_FILTER_MAX_K, a NULL pointer whose count is non-zero (status: always; filters and
+ * hist_out with n_filters > 0; code_out may be NULL), key products without key queries, both or neither score pointer, value_out without bin_value
+ * or with n_key_queries_total < 1, a workspace that is too small or not 256-byte aligned (needed when n_key_queries > 0).
+ * n == 0: zero histograms, every code -1, status as mms_ndcg_at_k (values 0); n_key_queries == 0: zero histograms and status; n_filters == 0: the
+ * status alone. */
+#define MMS_FILTER_MAX (1 << 16)
+#define MMS_FILTER_MAX_K 5
+int64_t mms_filter_sweep_workspace_bytes(int64_t n, int64_t n_key_queries, int64_t n_key_products);   /* a multiple of 256; -1 outside the caps */
+int mms_filter_sweep(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int64_t n,
+                     const int64_t* key_query, const int64_t* key_off, const int64_t* key_product, int64_t n_key_queries, int64_t n_key_products,
+                     const double* filters /* device [n_filters][2] = (gap, tie) */, int64_t n_filters, int32_t k /* 1..5 */, int32_t allow_missing,
+                     const double* bin_value /* device [(k+1)<<k] or NULL */, int64_t n_key_queries_total /* divisor of value_out */,
+                     void* workspace, int64_t workspace_bytes, int64_t* hist_out /* [n_filters][(k+1)<<k], zeroed by the call */,
+                     double* value_out /* [n_filters] or NULL; needs bin_value */, int32_t* code_out /* [n_filters][n_key_queries] or NULL */,
+                     int32_t* status /* [4] as mms_ndcg_at_k */, void* stream);
 
 /* accumulated hipEvent time (ms) and launch count of the GEMM kernels since the last reset;
  * enable = 1 brackets every GEMM launch with events on its stream (bench / roofline only) */

@@ -1876,6 +1876,34 @@ int mms_ndcg_weight_sweep(const int64_t* query_id, const int64_t* product_id, co
     return 0;
 }
 
+int64_t mms_filter_sweep_workspace_bytes(int64_t n, int64_t n_key_queries, int64_t n_key_products) {
+    if (mms_ndcg_workspace_bytes(n, n_key_queries, n_key_products) < 0) return -1;
+    return (int64_t)filter_sweep_workspace_bytes(n, n_key_queries, n_key_products);
+}
+
+int mms_filter_sweep(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int64_t n,
+                     const int64_t* key_query, const int64_t* key_off, const int64_t* key_product, int64_t n_key_queries, int64_t n_key_products,
+                     const double* filters, int64_t n_filters, int32_t k, int32_t allow_missing, const double* bin_value, int64_t n_key_queries_total,
+                     void* workspace, int64_t workspace_bytes, int64_t* hist_out, double* value_out, int32_t* code_out, int32_t* status, void* stream) {
+    // (the shared checks with a workspace of 0 bytes required: the sweep's own size is checked below)
+    const char* bad = ndcg_args(query_id, product_id, n, key_query, key_off, key_product, n_key_queries, n_key_products, workspace, INT64_MAX, status);
+    if (!bad && (n_filters < 0 || n_filters > MMS_FILTER_MAX)) bad = "n_filters must be in [0, MMS_FILTER_MAX]";
+    if (!bad && (k < 1 || k > MMS_FILTER_MAX_K)) bad = "k must be in [1, MMS_FILTER_MAX_K]";
+    if (!bad && (score_f32 != nullptr) == (score_f64 != nullptr)) bad = "exactly one of score_f32 / score_f64 must be given";
+    if (!bad && n_filters > 0 && (!filters || !hist_out)) bad = "null pointer";
+    if (!bad && value_out && !bin_value) bad = "value_out needs bin_value";
+    if (!bad && value_out && n_key_queries_total < 1) bad = "value_out needs n_key_queries_total >= 1";
+    if (!bad && n_key_queries > 0 && workspace_bytes < (int64_t)filter_sweep_workspace_bytes(n, n_key_queries, n_key_products))
+        bad = "workspace smaller than mms_filter_sweep_workspace_bytes(n, n_key_queries, n_key_products)";
+    if (bad) { g_err = std::string("mms_filter_sweep: ") + bad; return MMS_ERR_ARG; }
+    // (only enqueues: fills and at most fifteen kernels; no allocation, no synchronisation, nothing read back)
+    launch_filter_sweep(query_id, product_id, score_f32, score_f64, (int)n, key_query, key_off, key_product, (int)n_key_queries, (int)n_key_products, filters,
+                        n_filters, k, allow_missing != 0, bin_value, n_key_queries_total, workspace, hist_out, value_out, code_out, status, (hipStream_t)stream);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { g_err = std::string("mms_filter_sweep: ") + hipGetErrorString(e); return MMS_ERR_HIP; }
+    return 0;
+}
+
 int mms_create(const mms_config* cfg, mms_handle** out) {
     if (!cfg || !out) { g_err = "null argument"; return MMS_ERR_ARG; }
     *out = nullptr;

@@ -289,6 +289,14 @@ long long rank_workspace_bytes(long long n);
 void launch_rank_submission(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int n, double gap,
                             double tie, void* workspace, int max_queries, int64_t* out_query, int64_t* out_products, int32_t* out_count,
                             int32_t* status, hipStream_t st);
+// the (gap, tie)-independent stages of launch_rank_submission alone (status fill, table fills, k_rank_insert, k_rank_second), for a caller that applies
+// filters itself (filter_sweep.hip).  n > 0.  The views point into `workspace` (rank_workspace_bytes(n) bytes): enc[row] is the order-preserving image
+// of the row's score as a double (rank_tables.h), pslot[row] the slot of its product, or -1 for a row with a non-finite score or a reserved id; per
+// product slot: best = the largest image, bcnt = the rows that carry it, rest = the largest image below it (0: none), cnt = its rows.  status[2]
+// receives bits 0 (a repeated (query, product) pair), 1 and 3 of mms_rank_submission; the other status words stay 0.
+struct RankStats { const unsigned long long* enc; const int* pslot; const unsigned long long* best; const unsigned long long* rest; const int* cnt; const int* bcnt; };
+RankStats launch_rank_stats(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int n, void* workspace,
+                            int32_t* status, hipStream_t st);
 // ndcg.hip: relevance of every row against the answer key and the nDCG@k codes / histogram (mms_key_relevance / mms_ndcg_at_k check the arguments;
 // workspace of ndcg_workspace_bytes(n, Qa, Tk) bytes, 256-byte aligned).  out_code == nullptr: labels and status only.  Enqueues fills and at most
 // eight kernels on st; allocates nothing, waits for nothing.
@@ -309,3 +317,12 @@ void launch_ndcg_sweep(const int64_t* query_id, const int64_t* product_id, const
                        const int64_t* key_off, const int64_t* key_product, int Qa, int Tk, const double* weights, long long n_weights, int k,
                        int allow_missing, const double* bin_value, long long n_key_queries_total, void* workspace, int64_t* hist_out, double* value_out,
                        int32_t* status, hipStream_t st);
+// value_out[v] = (sum over all bins in bin order of double(hist[v][b]) * bin_value[b]) / total, every operation rounded on its own (k_sweep_value)
+void launch_hist_values(const int64_t* hist, const double* bin_value, long long n_hist, int bins, long long total, double* value_out, hipStream_t st);
+// filter_sweep.hip: nDCG@k histograms (and values, codes) of the submission rows under n_filters (gap, tie) pairs (mms_filter_sweep checks the arguments;
+// k in 1..5).  Enqueues fills and at most fifteen kernels on st; allocates nothing, waits for nothing.
+long long filter_sweep_workspace_bytes(long long n, long long n_key_queries, long long n_key_products);
+void launch_filter_sweep(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int n,
+                         const int64_t* key_query, const int64_t* key_off, const int64_t* key_product, int Qa, int Tk, const double* filters,
+                         long long n_filters, int k, int allow_missing, const double* bin_value, long long n_key_queries_total, void* workspace,
+                         int64_t* hist_out, double* value_out, int32_t* code_out, int32_t* status, hipStream_t st);

@@ -197,7 +197,10 @@ void launch_ndcg_sweep(const int64_t* query_id, const int64_t* product_id, const
             else launch_sweep_mp<8>(st, members, M, n, weights, W, k, Qa, L, s.rec, (u64*)hist_out, status);
         }
     }
-    if (value_out && W > 0)
-        hipLaunchKernelGGL(k_sweep_value, dim3((unsigned)((W + 255) / 256)), dim3(256), 0, st, (const u64*)hist_out, bin_value, W, bins,
-                           (double)n_key_queries_total, value_out);
+    if (value_out && W > 0) launch_hist_values(hist_out, bin_value, W, bins, n_key_queries_total, value_out, st);
+}
+
+void launch_hist_values(const int64_t* hist, const double* bin_value, long long n_hist, int bins, long long total, double* value_out, hipStream_t st) {
+    hipLaunchKernelGGL(k_sweep_value, dim3((unsigned)((n_hist + 255) / 256)), dim3(256), 0, st, (const u64*)hist, bin_value, n_hist, bins, (double)total,
+                       value_out);
 }

@@ -63,11 +63,6 @@ RankWs rank_layout(void* base, long long n) {
     return w;
 }
 
-__device__ __forceinline__ double dec_score(u64 e) {
-    const u64 b = (e >> 63) ? (e & 0x7FFFFFFFFFFFFFFFull) : ~e;
-    return __longlong_as_double((long long)b);
-}
-
 template <typename S>
 __global__ __launch_bounds__(256) void k_rank_insert(const long long* qid, const long long* pid, const S* score, int n, RankWs w, int* status) {
     const int r = blockIdx.x * 256 + threadIdx.x;
@@ -284,20 +279,32 @@ __global__ __launch_bounds__(256) void k_rank_select(const long long* pid, RankW
 
 long long rank_workspace_bytes(long long n) { return (long long)rank_layout(nullptr, n).total_bytes; }
 
-void launch_rank_submission(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int n, double gap,
-                            double tie, void* workspace, int max_queries, int64_t* out_query, int64_t* out_products, int32_t* out_count,
-                            int32_t* status, hipStream_t st) {
-    (void)hipMemsetAsync(status, 0, 16, st);
-    if (n <= 0) return;
+namespace {
+// the status fill, the two table fills and k_rank_insert / k_rank_second: everything that does not depend on (gap, tie).  n > 0.
+RankWs rank_stages(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int n, void* workspace,
+                   int32_t* status, hipStream_t st) {
     const RankWs w = rank_layout(workspace, n);
     (void)hipMemsetAsync(w.pkey, 0xFF, w.ff_bytes, st);
     (void)hipMemsetAsync(w.pbest, 0, w.zero_bytes, st);
-    const dim3 block(256), rows((n + 255) / 256), scan((n + SCAN_ROWS - 1) / SCAN_ROWS);
+    const dim3 block(256), rows((n + 255) / 256);
     const long long* q = (const long long*)query_id;
     const long long* p = (const long long*)product_id;
     if (score_f32) hipLaunchKernelGGL((k_rank_insert<float>), rows, block, 0, st, q, p, score_f32, n, w, status);
     else hipLaunchKernelGGL((k_rank_insert<double>), rows, block, 0, st, q, p, score_f64, n, w, status);
     hipLaunchKernelGGL(k_rank_second, rows, block, 0, st, n, w, status);
+    return w;
+}
+}  // namespace
+
+void launch_rank_submission(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int n, double gap,
+                            double tie, void* workspace, int max_queries, int64_t* out_query, int64_t* out_products, int32_t* out_count,
+                            int32_t* status, hipStream_t st) {
+    (void)hipMemsetAsync(status, 0, 16, st);
+    if (n <= 0) return;
+    const RankWs w = rank_stages(query_id, product_id, score_f32, score_f64, n, workspace, status, st);
+    const dim3 block(256), rows((n + 255) / 256), scan((n + SCAN_ROWS - 1) / SCAN_ROWS);
+    const long long* q = (const long long*)query_id;
+    const long long* p = (const long long*)product_id;
     hipLaunchKernelGGL(k_rank_survive, rows, block, 0, st, n, w, gap, tie);
     hipLaunchKernelGGL(k_rank_scan_sums, scan, block, 0, st, n, w);
     hipLaunchKernelGGL(k_rank_scan_top, dim3(1), block, 0, st, (int)scan.x, w, max_queries, status);
@@ -305,4 +312,11 @@ void launch_rank_submission(const int64_t* query_id, const int64_t* product_id, 
     hipLaunchKernelGGL(k_rank_scatter, rows, block, 0, st, n, w);
     const int sel_blocks = (int)std::min<long long>(2048, ((long long)n + 3) / 4);
     hipLaunchKernelGGL(k_rank_select, dim3(sel_blocks), block, 0, st, p, w, max_queries, status, (long long*)out_products, out_count);
+}
+
+RankStats launch_rank_stats(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int n, void* workspace,
+                            int32_t* status, hipStream_t st) {
+    (void)hipMemsetAsync(status, 0, 16, st);
+    const RankWs w = rank_stages(query_id, product_id, score_f32, score_f64, n, workspace, status, st);
+    return RankStats{w.enc, w.pslot, w.pbest, w.prest, w.pcnt, w.pbcnt};
 }

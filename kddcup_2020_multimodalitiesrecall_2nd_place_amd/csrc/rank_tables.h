@@ -18,6 +18,11 @@ __device__ __forceinline__ u64 enc_score(double d) {
     if (d == 0.0) b = 0;
     return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
+// the exact inverse of enc_score (up to the sign of zero)
+__device__ __forceinline__ double dec_score(u64 e) {
+    const u64 b = (e >> 63) ? (e & 0x7FFFFFFFFFFFFFFFull) : ~e;
+    return __longlong_as_double((long long)b);
+}
 __device__ __forceinline__ unsigned hash64(u64 x) {       // splitmix64 finaliser
     x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
     x ^= x >> 27; x *= 0x94D049BB133111EBull;

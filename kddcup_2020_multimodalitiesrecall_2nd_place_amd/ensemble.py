@@ -280,3 +280,52 @@ def fit_weights(query_id, product_id, members, rank_label, grid=None, k: int = 5
         values, _ = ndcg.ndcg_sweep_host(to_np(query_id), to_np(product_id), mem, grid, label_dict, k, allow_missing)
     index = int(np.argmax(values))                                               # the first row that attains the maximum
     return tuple(float(x) for x in grid[index]), float(values[index]), index, values
+
+
+def filter_grid(steps: int = 100, tie: float = TIE):
+    """The grid ``fit_filter`` searches by default: float64 [steps + 2, 2] rows ``(gap, tie)``.  Row 0 is ``(-inf, +inf)``, "no filter": every product
+    kept, every row a survivor, so the output row is the unfiltered top-5; rows ``1 + i`` are ``(i / steps, tie)`` for i = 0..steps."""
+    import numpy as np
+    if steps < 1:
+        raise ValueError("filter_grid: steps must be >= 1")
+    g = np.empty((steps + 2, 2), np.float64)
+    g[0] = (-np.inf, np.inf)
+    g[1:, 0] = np.arange(steps + 1, dtype=np.float64) / steps
+    g[1:, 1] = tie
+    return g
+
+
+def fit_filter(query_id, product_id, score, rank_label, filters=None, k: int = 5, allow_missing: bool = False, where: str = "device", info: dict = None):
+    """The uniqueness filter's constants as a result of the valid set: nDCG@k of the SUBMISSION rows (``ndcg.submission_codes``: filter, 1..4-survivor
+    fallback, dropped queries, divided by the whole key's length) for every row ``(gap, tie)`` of ``filters`` (default ``filter_grid()``), and the
+    winner -- the FIRST grid row that attains the maximum, the rule of ``fit_weights``.  -> ((gap, tie), value, index, values float64 numpy [G]).
+    ``where="device"``: ``ndcg.filter_sweep_device`` (``mms_filter_sweep``: one call for the whole grid); ONE synchronising read carries the status
+    and the values.  What the device does not do -- a (query, product) pair that occurs twice, a non-finite score in any row, a repeated key query,
+    a reserved id -- it detects: the values then come from ``ndcg.filter_sweep_host``, which ``where="host"`` runs directly; both give the same
+    floats, bit for bit.  A key query without rows raises ``KeyError`` unless ``allow_missing``.  ``info`` receives ``{"path", "flags"}``."""
+    import numpy as np
+
+    from . import ndcg
+    if where not in ("host", "device"):
+        raise ValueError("where must be 'host' or 'device', not %r" % (where,))
+    label_dict = rank_label.rank_label if isinstance(rank_label, ndcg.AnswerKey) else rank_label
+    filters = filter_grid() if filters is None else np.ascontiguousarray(filters, np.float64)
+    if filters.ndim != 2 or filters.shape[1] != 2 or filters.shape[0] == 0:
+        raise ValueError("fit_filter: the filters must be [G >= 1, 2] rows of (gap, tie)")
+    values, flags = None, 0
+    if where == "device" and len(label_dict):
+        import torch
+        dvalues, _, status = ndcg.filter_sweep_device(query_id, product_id, score, filters, rank_label, k, allow_missing)
+        host = torch.cat([status.to(torch.float64), dvalues]).cpu().numpy()      # the one synchronising read
+        flags = int(host[2])
+        if flags & ~ndcg.FLAG_MISSING_QUERY == 0:
+            if flags & ndcg.FLAG_MISSING_QUERY:                                  # only without allow_missing
+                raise KeyError("%d key queries have no rows" % int(host[3]))
+            values = host[4:].copy()
+    if info is not None:
+        info.update(path="device" if values is not None else "host", flags=flags)
+    if values is None:
+        to_np = lambda x: x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+        values, _, _ = ndcg.filter_sweep_host(to_np(query_id), to_np(product_id), to_np(score), filters, label_dict, k, allow_missing)
+    index = int(np.argmax(values))                                               # the first row that attains the maximum
+    return (float(filters[index, 0]), float(filters[index, 1])), float(values[index]), index, values

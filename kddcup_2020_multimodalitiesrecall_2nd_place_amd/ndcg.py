@@ -354,3 +354,118 @@ def ndcg_sweep_device(query_id, product_id, members, weights, rank_label, k: int
     if rc != 0:
         raise _lib.MmsError("mms_ndcg_weight_sweep failed (%d): %s" % (rc, l.mms_global_error().decode()))
     return values, hist, status
+
+
+# ---- filter sweep: nDCG@k of the SUBMISSION rows for every (gap, tie) pair of a grid (mms_filter_sweep, csrc/filter_sweep.hip) ----
+# per key query a code: -1 no rows in the table, -2 rows but no output row (no survivor: main.py:91-104 never writes the query, it scores 0),
+# otherwise mask | ideal << 8 over the products of its output row.
+FLAG_REPEATED_PAIR = 16                                                                    # status[2] bit 4 of mms_filter_sweep
+MAX_FILTERS, FILTER_MAX_K = 1 << 16, 5                                                     # MMS_FILTER_MAX, MMS_FILTER_MAX_K
+CODE_MISSING, CODE_DROPPED = -1, -2
+
+
+def codes_of_rows(rows: dict, present, rank_label: dict, k: int, allow_missing: bool):
+    """The codes of submission rows ``{str(query): [str(product), ..]}`` against the key; ``present``: the set of query ids (int) that have table rows."""
+    keys, truths = _key_lists(rank_label)
+    codes = np.empty(len(keys), np.int32)
+    for i, (kq, truth) in enumerate(zip(keys, truths)):
+        if kq not in present:
+            if not allow_missing:
+                raise KeyError(str(kq))
+            codes[i] = CODE_MISSING
+            continue
+        row = rows.get(str(kq))
+        if row is None:
+            codes[i] = CODE_DROPPED
+            continue
+        gt = set(truth)
+        mask = sum(1 << j for j, pp in enumerate(row[:k]) if int(pp) in gt)
+        codes[i] = mask | min(len(gt), k) << 8
+    return codes
+
+
+def _filter_k(k):
+    if not 1 <= k <= FILTER_MAX_K:
+        raise ValueError("k must be in 1..%d: a submission row holds five products" % FILTER_MAX_K)
+
+
+def submission_codes(query_id, product_id, score, rank_label: dict, gap, tie, k: int = 5, allow_missing: bool = False):
+    """Grades what is actually submitted: ``ensemble.submission_rows(query_id, product_id, score, gap, tie)`` -- the uniqueness filter, the
+    1..4-survivor fallback, the dropped no-survivor queries -- against the answer key.  -> int32 [len(rank_label)] in key order: -1 for a key query
+    without table rows (``KeyError`` unless ``allow_missing``), -2 for one with rows but no output row, otherwise ``mask | ideal << 8`` with bit j of
+    ``mask`` set when the j-th product of the output row is in ``set(truth)`` (j < min(k, products written)), ``ideal = min(len(set(truth)), k)``."""
+    from . import ensemble
+    _filter_k(k)
+    label_dict = rank_label.rank_label if isinstance(rank_label, AnswerKey) else rank_label
+    q = np.asarray(query_id).astype(np.int64).reshape(-1)
+    rows = ensemble.submission_rows(q, np.asarray(product_id).reshape(-1), np.asarray(score).reshape(-1), gap, tie)
+    return codes_of_rows(rows, set(np.unique(q).tolist()), label_dict, k, allow_missing)
+
+
+def _filter_array(filters):
+    f = np.ascontiguousarray(filters, np.float64)
+    if f.ndim != 2 or f.shape[1] != 2:
+        raise ValueError("filters must be [G, 2] rows of (gap, tie), not %s" % (tuple(f.shape),))
+    if f.shape[0] > MAX_FILTERS:
+        raise ValueError("at most %d filters per call" % MAX_FILTERS)
+    return f
+
+
+def filter_sweep_host(query_id, product_id, score, filters, rank_label: dict, k: int = 5, allow_missing: bool = False):
+    """The host form of the filter sweep and the reference of the device form: per row ``(gap, tie)`` of ``filters`` (float64 [G, 2])
+    ``submission_codes``, the histogram of the codes >= 0 and ``ndcg_from_hist`` of it over the WHOLE key -- a dropped or missing query costs its
+    share, as a grader of the submission file charges it.  -> (values float64 [G], hist int64 [G, (k + 1) << k], codes int32 [G, Qa]), numpy."""
+    f = _filter_array(filters)
+    _filter_k(k)
+    label_dict = rank_label.rank_label if isinstance(rank_label, AnswerKey) else rank_label
+    G, Qa = f.shape[0], len(label_dict)
+    values = np.empty(G, np.float64)
+    hist = np.empty((G, (k + 1) << k), np.int64)
+    codes = np.empty((G, Qa), np.int32)
+    for g in range(G):
+        codes[g] = submission_codes(query_id, product_id, score, label_dict, f[g, 0], f[g, 1], k, allow_missing)
+        hist[g] = hist_from_codes(codes[g], k)
+        values[g] = ndcg_from_hist(hist[g], k, Qa)
+    return values, hist, codes
+
+
+def filter_sweep_device(query_id, product_id, score, filters, rank_label, k: int = 5, allow_missing: bool = False, want_codes: bool = False):
+    """``mms_filter_sweep``: the filter sweep on the GPU in one call.  The rows are device tensors (used in place when int64 / fp32 or fp64 and
+    contiguous) or host arrays (copied up once); ``filters`` [G, 2] fp64; ``rank_label``: the ``{query: [products]}`` dict or an ``AnswerKey``.
+    -> (values float64 [G], hist int64 [G, (k + 1) << k], status int32 [4][, codes int32 [G, Qa] with ``want_codes``]), device tensors, equal to
+    ``filter_sweep_host`` -- integers entry for entry, values bit for bit -- while the flag word ``status[2]`` is zero.
+    Only enqueues on the current stream: nothing is read back, nothing waits."""
+    import torch
+
+    from . import lib as _lib
+    _filter_k(k)
+    (q, p, s), dev = _rows_on_device((query_id, product_id, score), ((torch.int64,), (torch.int64,), (torch.float64, torch.float32)), "filter_sweep_device")
+    flt = filters if torch.is_tensor(filters) else torch.from_numpy(_filter_array(filters))
+    flt = flt.to(device=dev, dtype=torch.float64, non_blocking=True).contiguous()
+    if flt.ndim != 2 or flt.shape[1] != 2 or flt.shape[0] > MAX_FILTERS:
+        raise ValueError("filters must be [G <= %d, 2] rows of (gap, tie), not %s" % (MAX_FILTERS, tuple(flt.shape)))
+    key = _key_on(rank_label, dev)
+    if key.n_queries == 0:
+        raise ValueError("filter_sweep_device: empty answer key")
+    n, G = s.shape[0], flt.shape[0]
+    l = _lib.load()
+    ws_bytes = l.mms_filter_sweep_workspace_bytes(n, key.n_queries, key.n_products)
+    if ws_bytes < 0:
+        raise ValueError("filter_sweep_device: %d rows, %d key queries, %d key products: the device path takes at most 2^22 rows / key products and 2^20 "
+                         "key queries" % (n, key.n_queries, key.n_products))
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)             # (the caching allocator returns 512-byte aligned blocks)
+    if (k, dev) not in _BIN_TABLES:
+        _BIN_TABLES[k, dev] = torch.from_numpy(bin_values(k).copy()).to(dev)
+    table = _BIN_TABLES[k, dev]
+    hist = torch.empty((G, (k + 1) << k), dtype=torch.int64, device=dev)
+    values = torch.empty((G,), dtype=torch.float64, device=dev)
+    codes = torch.empty((G, key.n_queries), dtype=torch.int32, device=dev) if want_codes else None
+    status = torch.empty((4,), dtype=torch.int32, device=dev)
+    f32 = s.dtype == torch.float32
+    sp = _ptr(s) or status.data_ptr()        # a non-NULL score pointer even for n == 0 (exactly one of the two must be given); never dereferenced then
+    rc = l.mms_filter_sweep(_ptr(q), _ptr(p), sp if f32 else None, None if f32 else sp, n, _ptr(key.key_query), _ptr(key.key_off), _ptr(key.key_product),
+                            key.n_queries, key.n_products, _ptr(flt), G, k, int(bool(allow_missing)), table.data_ptr(), key.n_queries, ws.data_ptr(), ws_bytes,
+                            _ptr(hist), _ptr(values), _ptr(codes), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    if rc != 0:
+        raise _lib.MmsError("mms_filter_sweep failed (%d): %s" % (rc, l.mms_global_error().decode()))
+    return (values, hist, status, codes) if want_codes else (values, hist, status)

@@ -485,6 +485,25 @@ class EnsembleScorer:
             scores_out.update(query_id=qid, product_id=pid, members=mem)
         return ensemble.fit_weights(qid, pid, mem, rank_label, grid, k, info=info)
 
+    def fit_filter_tsv_native(self, tsv_path, vocab_path, label_table, rank_label, filters=None, k: int = 5, labels: str = "answer",
+                              batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host", info: dict = None, scores_out: dict = None):
+        """A valid TSV file -> the uniqueness filter ``(gap, tie)`` that maximises the nDCG@k of the SUBMISSION rows against the answer key: ONE pass
+        as ``evaluate_tsv_native`` (merged scores left on the device, the zk members' label feed as ``labels`` says), then ``ensemble.fit_filter`` over
+        ``filters`` (default ``ensemble.filter_grid()``, 102 rows) on the fp64 copy of the merged scores in one library call (``mms_filter_sweep``).
+        -> ((gap, tie), value, index, values numpy [G]), the tuple of ``fit_filter``; pass the winner to ``submission_tsv_native(gap=, tie=)``.
+        ``scores_out`` (a dict) receives ``query_id`` / ``product_id`` (numpy) and ``score`` (device fp64)."""
+        from . import ensemble, ndcg
+        _check_eval_args("device", labels)
+        relabel = None
+        if labels == "answer":
+            rank_label = rank_label if isinstance(rank_label, ndcg.AnswerKey) else ndcg.AnswerKey(rank_label, self.zk.device)
+            relabel = _answer_labels(rank_label)
+        qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=False, relabel=relabel)
+        score = torch.cat([m for m, _ in out]).double() if out else torch.zeros(0, dtype=torch.float64, device=self.zk.device)
+        if scores_out is not None:
+            scores_out.update(query_id=qid, product_id=pid, score=score)
+        return ensemble.fit_filter(qid, pid, score, rank_label, filters, k, info=info)
+
     def score_tsv_native(self, tsv_path, vocab_path, label_table, batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host"):
         """``score_lines`` on a TSV file through libmmfeat, decode and scoring overlapped: a producer thread decodes span batch i+1
         three times (zk flavour, zk with the sen2forest rewrite, lxmert flavour; ctypes releases the GIL, each featurizer rotates
@@ -498,24 +517,26 @@ class EnsembleScorer:
         return qid, pid, torch.cat([m for m, _ in out]).double().cpu().numpy(), tuple(mem_all[k] for k in range(4))
 
     def submission_tsv_native(self, tsv_path, vocab_path, label_table, out_path=None, batch_pairs: int = 16384, threads: int = 0,
-                              feat_decode: str = "host", rank: str = "device"):
+                              feat_decode: str = "host", rank: str = "device", gap: float = None, tie: float = None):
         """TSV file -> submission rows (``{query: [p1..p5]}``, optionally written to ``out_path``): the pass of ``score_tsv_native`` with the merged
         scores left on the device -- no member scores, no score read-back --, the ids uploaded once, and the uniqueness filter + top-5 on the GPU
         (``ensemble.submission_rows_device``; ``rank="host"``: ``ensemble.submission_rows`` on the fp64 copy of the scores, what a caller of
-        ``score_tsv_native`` does).  Same rows either way."""
+        ``score_tsv_native`` does).  Same rows either way.  ``gap`` / ``tie``: the filter's constants (``None``: ``ensemble.GAP`` / ``ensemble.TIE``,
+        main.py's), e.g. the winner of ``fit_filter_tsv_native``; both rank forms take them."""
         from . import ensemble
         if feat_decode not in ("host", "device"):
             raise ValueError("feat_decode must be 'host' or 'device', not %r" % (feat_decode,))
         if rank not in ("host", "device"):
             raise ValueError("rank must be 'host' or 'device', not %r" % (rank,))
+        gap, tie = ensemble.GAP if gap is None else gap, ensemble.TIE if tie is None else tie
         qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=True)
         out = [m for m, _ in out]
         if not out:
-            rows = ensemble.submission_rows(qid, pid, np.zeros(0, np.float64))
+            rows = ensemble.submission_rows(qid, pid, np.zeros(0, np.float64), gap, tie)
         elif rank == "device":
-            rows = ensemble.submission_rows_device(qid, pid, torch.cat(out).double())
+            rows = ensemble.submission_rows_device(qid, pid, torch.cat(out).double(), gap, tie)
         else:
-            rows = ensemble.submission_rows(qid, pid, torch.cat(out).double().cpu().numpy())
+            rows = ensemble.submission_rows(qid, pid, torch.cat(out).double().cpu().numpy(), gap, tie)
         if out_path is not None:
             ensemble.write_submission(out_path, rows)
         return rows
