@@ -12,44 +12,37 @@
 //   launch_rank_stats    k_rank_insert / k_rank_second of rank.hip: score images, best / rows at best / max of the rest / rows per product, the
 //                        repeated-pair, non-finite and reserved-id flags (into a status block of its own)
 //   k_filter_pack        the listed rows in list order as 32-byte records: image, row << 1 | rel, d, e = |s - best|; thread 0 folds the rank flags into status[2]
-//   k_filter_unfiltered  one wavefront per key query: the relevance mask of its K best rows overall (k_select's rounds) -- the 1..4-survivor answer is
+//   k_filter_unfiltered  one wavefront per key query: the relevance mask of its K best rows overall (k_select's rounds: wave_next of rank_tables.h) -- the 1..4-survivor answer is
 //                        the same for every filter, so it is computed once per CALL
 //   k_filter_sweep<K>    a LANE owns a filter: a wavefront takes (key query i, tile of 64 filters) and walks the query's records serially (ndcg_sweep.hip's
 //                        decomposition).  The record's address is the same in all lanes: scalar loads, the next record requested while this one is
 //                        ranked.  Each lane decides survive on the record's d and e against its own (gap, tie), counts its survivors and inserts them
 //                        into a private top-K list in registers (static indexing, K comparisons and selects; the inserts themselves are selects, not branches).  At the end the
 //                        lane takes its survivor list (>= 5), the unfiltered mask (1..4) or code -2 (0).
-//                        Workgroups stride over (tile, slab of key queries) tasks; histogram: [bins][64] int32 counters in LDS per task (lane = bank),
+//                        Workgroups stride over (tile, slab of key queries) tasks (sweep_grid / sweep_task); histogram (sweep_zero / sweep_flush): [bins][64] int32 counters in LDS per task (lane = bank),
 //                        flushed with 64-bit global atomic adds of the non-zero counters.
 //   launch_hist_values   value[g] = (sum over all bins in bin order of double(hist[g][b]) * bin_value[b]) / n_key_queries_total (ndcg_sweep.hip)
 // Integer atomics only, and the order inside a list cannot matter because the selection key (image, row) is total: equal inputs give equal bytes.
 // No kernel waits on another workgroup.
 #include "rank_tables.h"
 
-#include <algorithm>
-
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int FSWEEP_MAX_BLOCKS = 4096;   // bounded grid: workgroups stride over the tasks
-constexpr int FSWEEP_TARGET_TASKS = 2048; // small grids: the key queries are cut into slabs until there are about this many tasks
-
 // One listed row as the hot loop streams it; aligned to its size: a wavefront fetches it with one scalar load.
 struct __attribute__((aligned(32))) FilterRec { u64 img; unsigned meta; unsigned pad; double d; double e; };      // meta = row << 1 | rel
 
-struct FilterWs { void* rank; int* rstatus; FilterRec* rec; int* umask; size_t total_bytes; };
+struct FilterWs { char* rank; int* rstatus; FilterRec* rec; int* umask; size_t total_bytes; };
 
 FilterWs filter_layout(void* base, long long n, long long Qa, long long Tk) {
     FilterWs f{};
-    char* p = (char*)base;
-    size_t o = up256((size_t)ndcg_workspace_bytes(n, Qa, Tk));
-    const size_t r = (size_t)(n > 0 ? n : 1), a = (size_t)(Qa > 0 ? Qa : 1);
-    f.rank = p + o; o += up256((size_t)rank_workspace_bytes(n));
-    f.rstatus = (int*)(p + o); o += 256;
-    f.rec = (FilterRec*)(p + o); o += up256(r * sizeof(FilterRec));
-    f.umask = (int*)(p + o); o += up256(a * 4);
-    f.total_bytes = o;
+    Carver cv{(char*)base, up256((size_t)ndcg_workspace_bytes(n, Qa, Tk))};
+    cv.take(f.rank, (size_t)rank_workspace_bytes(n));
+    cv.take(f.rstatus, 4);
+    cv.take(f.rec, (size_t)(n > 0 ? n : 1));
+    cv.take(f.umask, (size_t)(Qa > 0 ? Qa : 1));
+    f.total_bytes = cv.o;
     return f;
 }
 
@@ -81,37 +74,19 @@ __global__ __launch_bounds__(256) void k_filter_pack(int n, NdcgLists L, RankSta
     rec[x] = o;
 }
 
-// (image a, meta a) ranks before (image b, meta b): image descending -- the order of the scores as doubles with -0.0 == +0.0 --, then row ascending (the
-// meta words row << 1 | rel order as the rows: a list holds a row once)
-__device__ __forceinline__ bool ranks_before(u64 ia, unsigned ma, u64 ib, unsigned mb) { return ia > ib || (ia == ib && ma < mb); }
-
 // one wavefront per key query, wavefronts stride over the key: umask[i] = relevance bits of the K best rows of ALL its rows
 __global__ __launch_bounds__(256) void k_filter_unfiltered(int Qa, int K, NdcgLists L, const FilterRec* __restrict__ rec, int* __restrict__ umask) {
     const int lane = threadIdx.x & 63;
     const int waves = gridDim.x * 4;
     for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < Qa; i += waves) {
         const int cnt = L.cnt[i], off = L.off[i];
-        u64 pe = ~0ull;                                   // previous pick: every image is below ~0
-        unsigned pm = 0, mask = 0;
-        bool first = true;
+        Pick prev{~0ull, 0};                              // previous pick: every image is below ~0
+        unsigned mask = 0;
         for (int j = 0; j < K; ++j) {
-            u64 be = 0;                                   // no image is 0
-            unsigned bm = 0xFFFFFFFFu;
-            for (int x = lane; x < cnt; x += 64) {
-                const u64 e = rec[off + x].img;
-                const unsigned m = rec[off + x].meta;
-                if (!first && !ranks_before(pe, pm, e, m)) continue;         // after the previous pick
-                if (ranks_before(e, m, be, bm)) { be = e; bm = m; }
-            }
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                const u64 oe = __shfl_xor(be, d);
-                const unsigned om = __shfl_xor(bm, d);
-                if (ranks_before(oe, om, be, bm)) { be = oe; bm = om; }
-            }
-            if (be == 0) break;                           // exhausted: the remaining places carry relevance 0
-            mask |= (bm & 1u) << j;
-            pe = be; pm = bm; first = false;
+            const Pick b = wave_next(cnt, prev, [&](int x) { return Pick{rec[off + x].img, rec[off + x].meta}; });
+            if (b.img == 0) break;                        // exhausted: the remaining places carry relevance 0
+            mask |= (b.tie & 1u) << j;
+            prev = b;
         }
         if (lane == 0) umask[i] = (int)mask;
     }
@@ -123,17 +98,13 @@ __global__ __launch_bounds__(256) void k_filter_sweep(const double* __restrict__
     constexpr int BINS = (K + 1) << K;
     __shared__ int counters[BINS * 64];                                      // [bin][lane of the tile]
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);    // (scalar: the query walk is wave-uniform)
-    const int per = (Qa + slabs - 1) / slabs;
     for (long long t = blockIdx.x; t < tasks; t += gridDim.x) {
-        const long long tile = t / slabs;
-        const int slab = (int)(t - tile * slabs);
-        const long long g = tile * 64 + lane;
+        const SweepTask task = sweep_task(t, slabs, Qa);
+        const long long g = task.tile * 64 + lane;
         const bool live = g < G;
         const double gap = live ? filters[g * 2] : 0.0, tie = live ? filters[g * 2 + 1] : 0.0;
-        for (int x = threadIdx.x; x < BINS * 64; x += 256) counters[x] = 0;
-        __syncthreads();
-        const int q1 = min(Qa, (slab + 1) * per);
-        for (int i = slab * per + wv; i < q1; i += 4) {                      // (i, cnt, off: the same in every lane of the wavefront)
+        sweep_zero<BINS>(counters);
+        for (int i = task.q0 + wv; i < task.q1; i += 4) {                     // (i, cnt, off: the same in every lane of the wavefront)
             const int cnt = L.cnt[i];
             if (cnt == 0) {                                                  // a key query without rows: no histogram entry
                 if (code_out && live) code_out[(size_t)g * Qa + i] = -1;
@@ -154,7 +125,8 @@ __global__ __launch_bounds__(256) void k_filter_sweep(const double* __restrict__
                 const bool sv = !(cur.d < gap) && cur.e < tie;
                 cur = nxt;
                 ns += sv ? 1 : 0;
-                // branch-free insertion: c[j] = this survivor ranks before place j (monotone in j: the list is sorted by a total order)
+                // TopK::insert's steps, written here: through the shared template this loop compiles branch-free instead of to the exec regions it
+                // was measured with (profiles/rd13_rank_family_refactor.txt).  c[j] = this survivor ranks before place j (monotone in j)
                 bool c[K];
 #pragma unroll
                 for (int j = 0; j < K; ++j) c[j] = sv && ranks_before(img, meta, E[j], R[j]);
@@ -176,13 +148,7 @@ __global__ __launch_bounds__(256) void k_filter_sweep(const double* __restrict__
                 if (code_out) code_out[(size_t)g * Qa + i] = ns > 0 ? (int)(mask | (ideal << 8)) : -2;
             }
         }
-        __syncthreads();
-        for (int x = threadIdx.x; x < BINS * 64; x += 256) {
-            const int c = counters[x];
-            const long long gg = tile * 64 + (x & 63);
-            if (c != 0 && gg < G) atomicAdd(&hist[(size_t)gg * BINS + (x >> 6)], (u64)c);
-        }
-        __syncthreads();
+        sweep_flush<BINS>(counters, task.tile, G, hist);
     }
 }
 
@@ -208,11 +174,8 @@ void launch_filter_sweep(const int64_t* query_id, const int64_t* product_id, con
             if (G > 0) {
                 const int sel_blocks = (int)std::min<long long>(2048, ((long long)Qa + 3) / 4);
                 hipLaunchKernelGGL(k_filter_unfiltered, dim3(sel_blocks), dim3(256), 0, st, Qa, k, L, (const FilterRec*)f.rec, f.umask);
-                const long long tiles = (G + 63) / 64;
-                const int slabs = (int)std::max<long long>(1, std::min<long long>((FSWEEP_TARGET_TASKS + tiles - 1) / tiles, ((long long)Qa + 3) / 4));
-                const long long tasks = tiles * slabs;
-                const dim3 grid((unsigned)std::min<long long>(tasks, FSWEEP_MAX_BLOCKS)), block(256);
-#define FSWEEP_CASE(K) case K: hipLaunchKernelGGL((k_filter_sweep<K>), grid, block, 0, st, filters, G, Qa, slabs, tasks, L, (const FilterRec*)f.rec, (const int*)f.umask, (u64*)hist_out, code_out); break
+                const SweepGrid sg = sweep_grid(G, Qa);
+#define FSWEEP_CASE(K) case K: hipLaunchKernelGGL((k_filter_sweep<K>), dim3(sg.grid), dim3(256), 0, st, filters, G, Qa, sg.slabs, sg.tasks, L, (const FilterRec*)f.rec, (const int*)f.umask, (u64*)hist_out, code_out); break
                 switch (k) {
                     FSWEEP_CASE(1); FSWEEP_CASE(2); FSWEEP_CASE(3); FSWEEP_CASE(4);
                     default: FSWEEP_CASE(5);

@@ -16,9 +16,9 @@
 //                    distinct[i] counts the pairs that were new
 //   k_rows           per row: key index of its query (looked up once per RUN of equal query ids inside a wavefront, wave_run), membership of
 //                    (key index, product) in the set, score image, rows per key query (atomic add once per run)
-//   k_scan_*         exclusive scan of the per-key row counts (block sums / top / apply): list offsets, the status totals
-//   k_scatter        rows grouped by key query (counting sort by the offsets; the order inside a list does not matter)
-//   k_select         one wavefront per key query: k rounds of a wave-wide arg-max over (image, row) below the previous pick, looping over
+//   k_scan_*         exclusive scan of the per-key row counts (block sums / top / apply; block_scan and scan_top of rank_tables.h): list offsets, the status totals
+//   k_scatter        rows grouped by key query (counting sort by the offsets, scatter_rows; the order inside a list does not matter)
+//   k_select         one wavefront per key query: k rounds of a wave-wide arg-max over (image, row) below the previous pick (wave_next), looping over
 //                    the list when it is longer than a wavefront
 // mms_key_relevance stops after k_scan_top (it needs the totals only).  No workgroup waits on another: the stages meet at kernel boundaries.
 // The weight sweep (ndcg_sweep.hip, mms_ndcg_weight_sweep) runs everything up to k_scatter with no score (launch_ndcg_lists) and ranks the lists itself.
@@ -46,18 +46,16 @@ NdcgWs ndcg_layout(void* base, long long n, long long Qa, long long Tk) {
     while (capq < 2 * Qa) capq <<= 1;
     while (capp < 2 * Tk) capp <<= 1;
     w.qmask = (unsigned)(capq - 1); w.pmask = (unsigned)(capp - 1);
-    char* p = (char*)base;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { char* q = p + o; o += up256(bytes); return q; };
+    Carver cv{(char*)base, 0};
     const size_t r = (size_t)(n > 0 ? n : 1), a = (size_t)(Qa > 0 ? Qa : 1), nb = (a + SCAN_KEYS - 1) / SCAN_KEYS;
-    w.kqkey = (long long*)take((size_t)capq * 8); w.pkey = (long long*)take((size_t)capp * 8); w.pairkey = (long long*)take((size_t)capp * 8);
-    w.ff_bytes = o;
-    w.cnt = (int*)take(a * 4); w.fill = (int*)take(a * 4); w.distinct = (int*)take(a * 4); w.missing = (int*)take(4);
-    w.zero_bytes = o - w.ff_bytes;
-    w.kqval = (int*)take((size_t)capq * 4);
-    w.off = (int*)take(a * 4); w.bsum = (int*)take(nb * 4);
-    w.enc = (u64*)take(r * 8); w.rowqi = (int*)take(r * 4); w.list = (int*)take(r * 4); w.rel = (unsigned char*)take(r);
-    w.total_bytes = o;
+    cv.take(w.kqkey, (size_t)capq); cv.take(w.pkey, (size_t)capp); cv.take(w.pairkey, (size_t)capp);
+    w.ff_bytes = cv.o;
+    cv.take(w.cnt, a); cv.take(w.fill, a); cv.take(w.distinct, a); cv.take(w.missing, 1);
+    w.zero_bytes = cv.o - w.ff_bytes;
+    cv.take(w.kqval, (size_t)capq);
+    cv.take(w.off, a); cv.take(w.bsum, nb);
+    cv.take(w.enc, r); cv.take(w.rowqi, r); cv.take(w.list, r); cv.take(w.rel, r);
+    w.total_bytes = cv.o;
     return w;
 }
 
@@ -111,7 +109,7 @@ __global__ __launch_bounds__(256) void k_rows(const long long* qid, const long l
         int flags = 0;
         if (score) {
             const double s = (double)score[r];
-            if (!(fabs(s) <= 1.79769313486231570815e308)) flags |= 2;       // NaN, +-inf
+            if (!finite_score(s)) flags |= 2;
             w.enc[r] = enc_score(s);
         }
         if (q == RANK_EMPTY || p == RANK_EMPTY) flags |= 8;
@@ -141,29 +139,6 @@ __global__ __launch_bounds__(256) void k_rows(const long long* qid, const long l
     }
 }
 
-// exclusive scan of one int per thread over the 256 threads of a workgroup; *total = the workgroup's sum
-__device__ __forceinline__ int block_scan(int v, int* total) {
-    __shared__ int wsum[4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(inc, d);
-        if (lane >= d) inc += o;
-    }
-    if (lane == 63) wsum[wv] = inc;
-    __syncthreads();
-    int base = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (i < wv) base += wsum[i];
-        tot += wsum[i];
-    }
-    *total = tot;
-    __syncthreads();
-    return base + inc - v;
-}
-
 __global__ __launch_bounds__(256) void k_scan_sums(int Qa, NdcgWs w) {
     const int i0 = blockIdx.x * SCAN_KEYS + threadIdx.x * 4;
     int t = 0, miss = 0;
@@ -182,16 +157,7 @@ __global__ __launch_bounds__(256) void k_scan_sums(int Qa, NdcgWs w) {
 
 // one workgroup: block sums -> exclusive prefixes (in place); the status totals
 __global__ __launch_bounds__(256) void k_scan_top(int nb, int Qa, int allow_missing, NdcgWs w, int* status) {
-    const int per = (nb + 255) / 256, b0 = threadIdx.x * per;
-    int t = 0;
-    for (int i = b0; i < b0 + per && i < nb; ++i) t += w.bsum[i];
-    int total;
-    int run = block_scan(t, &total);
-    for (int i = b0; i < b0 + per && i < nb; ++i) {
-        const int v = w.bsum[i];
-        w.bsum[i] = run;
-        run += v;
-    }
+    const int total = scan_top(w.bsum, nb);
     if (threadIdx.x == 0) {
         const int miss = *w.missing;
         status[0] = Qa - miss; status[1] = total; status[3] = miss;
@@ -214,15 +180,7 @@ __global__ __launch_bounds__(256) void k_scan_apply(int Qa, NdcgWs w) {
 }
 
 __global__ __launch_bounds__(256) void k_scatter(int n, NdcgWs w) {
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    const int qi = r < n ? w.rowqi[r] : -1;
-    const bool live = qi >= 0;
-    const Run run = wave_run((long long)qi, live);
-    const int lane = threadIdx.x & 63;
-    int base = 0;
-    if (live && lane == run.head) base = w.off[qi] + atomicAdd(&w.fill[qi], run.len);
-    base = __shfl(base, run.head);
-    if (live) w.list[base + lane - run.head] = r;          // offsets + fills stay below the counted rows: inside [0, n)
+    scatter_rows(n, w.rowqi, w.off, w.fill, w.list);
 }
 
 // one wavefront per key query, wavefronts stride over the key
@@ -231,27 +189,15 @@ __global__ __launch_bounds__(256) void k_select(const long long* pid, int Qa, in
     const int waves = gridDim.x * 4;
     for (int i = blockIdx.x * 4 + (threadIdx.x >> 6); i < Qa; i += waves) {
         const int cnt = w.cnt[i], off = w.off[i];
-        u64 pe = ~0ull;                                   // previous pick: every image is below ~0
-        int pr = -1;
+        Pick prev{~0ull, 0};                              // previous pick: every image is below ~0
         unsigned mask = 0;
         for (int j = 0; j < k; ++j) {
-            u64 be = 0;                                   // no image is 0
-            int br = 0x7FFFFFFF;
-            for (int x = lane; x < cnt; x += 64) {
+            const Pick b = wave_next(cnt, prev, [&](int x) {             // (image descending, row ascending)
                 const int r = w.list[off + x];
-                const u64 e = w.enc[r];
-                if (!(e < pe || (e == pe && r > pr))) continue;          // after the previous pick in (image descending, row ascending)
-                if (e > be || (e == be && r < br)) { be = e; br = r; }
-            }
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                const u64 oe = __shfl_xor(be, d);
-                const int orr = __shfl_xor(br, d);
-                if (oe > be || (oe == be && orr < br)) { be = oe; br = orr; }
-            }
-            long long prod = -1;
-            if (be != 0) { prod = pid[br]; mask |= (unsigned)w.rel[br] << j; pe = be; pr = br; }
-            else pe = 0;                                  // exhausted: nothing is below image 0, the remaining rounds write -1
+                return Pick{w.enc[r], (unsigned)r};
+            });
+            long long prod = -1;                          // exhausted: prev stays, so the remaining rounds find nothing either and write -1
+            if (b.img != 0) { prod = pid[b.tie]; mask |= (unsigned)w.rel[b.tie] << j; prev = b; }
             if (out_topk && lane == 0) out_topk[(long long)i * k + j] = prod;
         }
         if (lane == 0) {

@@ -11,27 +11,23 @@
 //   k_sweep<K, MP>      a LANE owns a weight vector: a wavefront takes (key query i, tile of 64 weight vectors) and walks the query's packed rows
 //                       serially.  The record's address is the same in all lanes: scalar loads, the next record requested while this one is
 //                       ranked.  Each lane forms its own score_v[r] and inserts (score, row, rel) into a private top-K list in registers (K a
-//                       template parameter: static indexing; K comparisons and selects, no data-dependent branch -- with 64 weight vectors per
+//                       template parameter: static indexing; K comparisons and selects, no data-dependent branch: TopK of rank_tables.h -- with 64 weight vectors per
 //                       wavefront SOME lane inserts on most rows).  No cross-lane operation, no LDS for the ranking, 64 busy lanes whatever the
 //                       rows per query -- the opposite decomposition to k_select (a lane per row), which would idle more than half a wavefront
 //                       on the valid set's 9 - 30 rows per query and pay six shuffle steps per pick and per weight.
-//                       Workgroups stride over (tile, slab of key queries) tasks, the four waves of a workgroup over the slab's queries.
-//                       Histogram, K <= 5 (64 x bins x 4 B <= 48 KiB): [bins][64] int32 counters in LDS per task (lane = bank: conflict-free),
-//                       flushed with 64-bit global atomic adds of the non-zero counters; K >= 6: 64-bit global atomic adds directly.
+//                       Workgroups stride over (tile, slab of key queries) tasks (sweep_grid / sweep_task), the four waves of a workgroup over the slab's queries.
+//                       Histogram, K <= 5 (64 x bins x 4 B <= 48 KiB): [bins][64] int32 counters in LDS per task (lane = bank: conflict-free;
+//                       sweep_zero / sweep_flush), flushed with 64-bit global atomic adds of the non-zero counters; K >= 6: 64-bit global atomic adds directly.
 //   k_sweep_value       value[v] = (sum over all bins in bin order of double(hist[v][b]) * bin_value[b]) / n_key_queries_total, each
 //                       operation rounded on its own: ndcg.ndcg_from_hist bit for bit (an empty bin adds +0.0 to a non-negative sum).
 // Integer atomics only, and the order inside a list cannot matter because the selection key (score with -0.0 == +0.0, row) is total: equal inputs give equal bytes.
 #include "rank_tables.h"
-
-#include <algorithm>
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int SWEEP_LDS_MAX_K = 5;       // (K + 1) << K bins x 64 lanes x 4 B: 48 KiB at K = 5
-constexpr int SWEEP_MAX_BLOCKS = 4096;   // bounded grid: workgroups stride over the tasks
-constexpr int SWEEP_TARGET_TASKS = 2048; // small grids: the key queries are cut into slabs until there are about this many tasks
 
 // One listed row as the hot loop streams it: the member scores (zero past the M-th), and row << 1 | rel.  MP = 4 (M <= 4) or 8: the record is
 // 8 x MP bytes and aligned to its size, so a wavefront fetches it with one or two scalar loads.
@@ -40,14 +36,13 @@ struct __attribute__((aligned(8 * MP))) SweepRec { float s[MP]; unsigned meta; u
 
 inline int sweep_mp(int M) { return M <= 4 ? 4 : 8; }
 
-struct SweepWs { void* rec; size_t total_bytes; };
+struct SweepWs { char* rec; size_t total_bytes; };
 
 SweepWs sweep_layout(void* base, long long n, long long Qa, long long Tk, int M) {
     SweepWs s{};
-    size_t o = up256((size_t)ndcg_workspace_bytes(n, Qa, Tk));
-    const size_t r = (size_t)(n > 0 ? n : 1);
-    s.rec = (char*)base + o; o += up256(r * (size_t)sweep_mp(M) * 8);
-    s.total_bytes = o;
+    Carver cv{(char*)base, up256((size_t)ndcg_workspace_bytes(n, Qa, Tk))};
+    cv.take(s.rec, (size_t)(n > 0 ? n : 1) * (size_t)sweep_mp(M) * 8);
+    s.total_bytes = cv.o;
     return s;
 }
 
@@ -65,11 +60,7 @@ __global__ __launch_bounds__(256) void k_sweep_pack(const float* __restrict__ me
     rec[x] = o;
 }
 
-// (score a, row a) ranks before (score b, row b): score descending with -0.0 == +0.0 -- the IEEE comparison of finite doubles, which orders them as
-// enc_score's images do --, then row ascending (the meta words row << 1 | rel order as the rows: a list holds a row once).  A non-finite score is
-// flagged, and with a flag the outputs are unspecified.
-__device__ __forceinline__ bool ranks_before(double sa, unsigned ma, double sb, unsigned mb) { return sa > sb || (sa == sb && ma < mb); }
-
+// The lists are ranked on the scores as doubles (ranks_before<double>).  A non-finite score is flagged, and with a flag the outputs are unspecified.
 // A padded member (m >= M) has score 0 and weight 0: its term adds +0.0, which can change the sign of a zero sum and nothing else -- and -0.0
 // ranks as +0.0.  So the MP-term sum ranks, and flags, exactly as the M-term sum of the contract.
 template <int K, int MP, bool LDS>
@@ -78,29 +69,21 @@ __global__ __launch_bounds__(256) void k_sweep(const double* __restrict__ weight
     constexpr int BINS = (K + 1) << K;
     __shared__ int counters[LDS ? BINS * 64 : 1];                            // [bin][lane of the tile]
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);    // (scalar: the query walk is wave-uniform)
-    const int per = (Qa + slabs - 1) / slabs;
     bool bad = false;
     for (long long t = blockIdx.x; t < tasks; t += gridDim.x) {
-        const long long tile = t / slabs;
-        const int slab = (int)(t - tile * slabs);
-        const long long v = tile * 64 + lane;
+        const SweepTask task = sweep_task(t, slabs, Qa);
+        const long long v = task.tile * 64 + lane;
         const bool live = v < W;
         double w[MP];
 #pragma unroll
         for (int m = 0; m < MP; ++m) w[m] = (live && m < M) ? weights[v * M + m] : 0.0;
-        if (LDS) {
-            for (int x = threadIdx.x; x < BINS * 64; x += 256) counters[x] = 0;
-            __syncthreads();
-        }
-        const int q1 = min(Qa, (slab + 1) * per);
-        for (int i = slab * per + wv; i < q1; i += 4) {                      // (i, cnt, off: the same in every lane of the wavefront)
+        if (LDS) sweep_zero<BINS>(counters);
+        for (int i = task.q0 + wv; i < task.q1; i += 4) {                     // (i, cnt, off: the same in every lane of the wavefront)
             const int cnt = L.cnt[i];
             if (cnt == 0) continue;                                          // a key query without rows: no histogram entry
             const int off = L.off[i];
-            double E[K];                                                     // the K best so far, best first; an empty place: -inf, row 2^31 - 1, rel 0
-            unsigned R[K];
-#pragma unroll
-            for (int j = 0; j < K; ++j) { E[j] = -__builtin_huge_val(); R[j] = 0xFFFFFFFEu; }
+            TopK<K, double> top;                                             // the K best so far; an empty place: -inf
+            top.clear(-__builtin_huge_val());
             const int end = off + cnt;
             SweepRec<MP> cur = rec[off];
             for (int x = off; x < end; ++x) {
@@ -113,37 +96,16 @@ __global__ __launch_bounds__(256) void k_sweep(const double* __restrict__ weight
                     s = s + prod;
                 }
                 cur = nxt;
-                bad |= live && !(fabs(s) <= 1.79769313486231570815e308);     // NaN, +-inf
-                // branch-free insertion: c[j] = this row ranks before place j (monotone in j: the list is sorted by a total order)
-                bool c[K];
-#pragma unroll
-                for (int j = 0; j < K; ++j) c[j] = ranks_before(s, meta, E[j], R[j]);
-#pragma unroll
-                for (int j = K - 1; j >= 1; --j) {
-                    E[j] = c[j - 1] ? E[j - 1] : (c[j] ? s : E[j]);
-                    R[j] = c[j - 1] ? R[j - 1] : (c[j] ? meta : R[j]);
-                }
-                E[0] = c[0] ? s : E[0];
-                R[0] = c[0] ? meta : R[0];
+                bad |= live && !finite_score(s);
+                top.insert(true, s, meta);
             }
-            unsigned mask = 0;
-#pragma unroll
-            for (int j = 0; j < K; ++j) mask |= (R[j] & 1u) << j;            // an empty place carries relevance 0
-            const unsigned bin = ((unsigned)min(max(L.distinct[i], 0), K) << K) | mask;
+            const unsigned bin = ((unsigned)min(max(L.distinct[i], 0), K) << K) | top.rel_mask();
             if (live) {
                 if (LDS) atomicAdd(&counters[bin * 64 + lane], 1);
                 else atomicAdd(&hist[(size_t)v * BINS + bin], 1ull);
             }
         }
-        if (LDS) {
-            __syncthreads();
-            for (int x = threadIdx.x; x < BINS * 64; x += 256) {
-                const int c = counters[x];
-                const long long vv = tile * 64 + (x & 63);
-                if (c != 0 && vv < W) atomicAdd(&hist[(size_t)vv * BINS + (x >> 6)], (u64)c);
-            }
-            __syncthreads();
-        }
+        if (LDS) sweep_flush<BINS>(counters, task.tile, W, hist);
     }
     if (bad) atomicOr(&status[2], 2);
 }
@@ -166,11 +128,8 @@ void launch_sweep_mp(hipStream_t st, const float* members, int M, int n, const d
                      u64* hist, int* status) {
     SweepRec<MP>* rec = (SweepRec<MP>*)records;
     hipLaunchKernelGGL((k_sweep_pack<MP>), dim3((n + 255) / 256), dim3(256), 0, st, members, M, n, L, (const int*)status, rec);
-    const long long tiles = (W + 63) / 64;
-    const int slabs = (int)std::max<long long>(1, std::min<long long>((SWEEP_TARGET_TASKS + tiles - 1) / tiles, ((long long)Qa + 3) / 4));
-    const long long tasks = tiles * slabs;
-    const dim3 grid((unsigned)std::min<long long>(tasks, SWEEP_MAX_BLOCKS)), block(256);
-#define SWEEP_CASE(K) case K: hipLaunchKernelGGL((k_sweep<K, MP, K <= SWEEP_LDS_MAX_K>), grid, block, 0, st, weights, W, M, Qa, slabs, tasks, L, rec, hist, status); break
+    const SweepGrid g = sweep_grid(W, Qa);
+#define SWEEP_CASE(K) case K: hipLaunchKernelGGL((k_sweep<K, MP, K <= SWEEP_LDS_MAX_K>), dim3(g.grid), dim3(256), 0, st, weights, W, M, Qa, g.slabs, g.tasks, L, rec, hist, status); break
     switch (k) {
         SWEEP_CASE(1); SWEEP_CASE(2); SWEEP_CASE(3); SWEEP_CASE(4); SWEEP_CASE(5); SWEEP_CASE(6); SWEEP_CASE(7);
         default: SWEEP_CASE(8);

@@ -17,9 +17,9 @@
 //                    third table -- a pair that is already there raises flag bit 0
 //   k_rank_survive   second, keep_product, survive per row; survivors per query
 //   k_rank_scan_*    one exclusive scan over the rows of four per-row values that are non-zero on a query's FIRST row only: "class >= 5",
-//                    "class 1..4", "rows of the query", "is a first row" -> output position, list offset, counts (block sums / top / apply)
-//   k_rank_scatter   rows grouped by query (counting sort by the offsets above; the order inside a list does not matter)
-//   k_rank_select    one wavefront per output row: five rounds of a wave-wide arg-max over (image, row) below the previous pick
+//                    "class 1..4", "rows of the query", "is a first row" -> output position, list offset, counts (block sums / top / apply; block_scan and scan_top of rank_tables.h)
+//   k_rank_scatter   rows grouped by query (counting sort by the offsets above, scatter_rows; the order inside a list does not matter)
+//   k_rank_select    one wavefront per output row: five rounds of a wave-wide arg-max over (image, row) below the previous pick (wave_next)
 // The only atomics are integer max / min / add / or / compare-and-swap whose final memory value is independent of the arrival order, and
 // the values they return (a list position in k_rank_scatter) never reach the output: equal inputs give bit-equal outputs.
 // Rows of one query are mostly adjacent, so the query-side atomics are issued once per RUN of equal query ids inside a wavefront
@@ -45,21 +45,19 @@ RankWs rank_layout(void* base, long long n) {
     int cap = 1024;
     while (cap < 2 * n) cap <<= 1;
     w.cap = cap; w.mask = (unsigned)(cap - 1);
-    char* p = (char*)base;
-    size_t o = 0;
-    auto take = [&](size_t bytes) { char* q = p + o; o += up256(bytes); return q; };
+    Carver cv{(char*)base, 0};
     const size_t c = (size_t)cap, r = (size_t)(n > 0 ? n : 1), nb = (r + SCAN_ROWS - 1) / SCAN_ROWS;
-    w.pkey = (long long*)take(c * 8); w.qkey = (long long*)take(c * 8); w.pairkey = (long long*)take(c * 8);
-    w.ff_bytes = o;
-    w.pbest = (u64*)take(c * 8); w.prest = (u64*)take(c * 8);
-    w.pcnt = (int*)take(c * 4); w.pbcnt = (int*)take(c * 4); w.qcnt = (int*)take(c * 4); w.qsurv = (int*)take(c * 4); w.qfill = (int*)take(c * 4);
-    w.qfirst_inv = (unsigned*)take(c * 4);
-    w.zero_bytes = o - w.ff_bytes;
-    w.qoff = (int*)take(c * 4);
-    w.enc = (u64*)take(r * 8); w.pslot = (int*)take(r * 4); w.qslot = (int*)take(r * 4); w.qlist = (int*)take(r * 4); w.qsel = (int*)take(r * 4);
-    w.bsum = (int4*)take(nb * 16); w.surv = (unsigned char*)take(r);
-    w.hdr = (int*)take(16);
-    w.total_bytes = o;
+    cv.take(w.pkey, c); cv.take(w.qkey, c); cv.take(w.pairkey, c);
+    w.ff_bytes = cv.o;
+    cv.take(w.pbest, c); cv.take(w.prest, c);
+    cv.take(w.pcnt, c); cv.take(w.pbcnt, c); cv.take(w.qcnt, c); cv.take(w.qsurv, c); cv.take(w.qfill, c);
+    cv.take(w.qfirst_inv, c);
+    w.zero_bytes = cv.o - w.ff_bytes;
+    cv.take(w.qoff, c);
+    cv.take(w.enc, r); cv.take(w.pslot, r); cv.take(w.qslot, r); cv.take(w.qlist, r); cv.take(w.qsel, r);
+    cv.take(w.bsum, nb); cv.take(w.surv, r);
+    cv.take(w.hdr, 4);
+    w.total_bytes = cv.o;
     return w;
 }
 
@@ -72,7 +70,7 @@ __global__ __launch_bounds__(256) void k_rank_insert(const long long* qid, const
     if (live) {
         q = qid[r]; p = pid[r]; s = (double)score[r];
         int flags = 0;
-        if (!(fabs(s) <= 1.79769313486231570815e308)) flags |= 2;       // NaN, +-inf
+        if (!finite_score(s)) flags |= 2;
         if (q == RANK_EMPTY || p == RANK_EMPTY) flags |= 8;
         if (flags) { atomicOr(&status[2], flags); live = false; w.pslot[r] = -1; w.qslot[r] = -1; }
     }
@@ -147,54 +145,20 @@ __device__ __forceinline__ int4 scan_vals(const RankWs& w, int r, int n) {
     }
     return v;
 }
-__device__ __forceinline__ int4 add4(int4 a, int4 b) { return make_int4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__device__ __forceinline__ int4 shfl_up4(int4 a, int d) { return make_int4(__shfl_up(a.x, d), __shfl_up(a.y, d), __shfl_up(a.z, d), __shfl_up(a.w, d)); }
-
-// exclusive scan of one int4 per thread over the 256 threads of a workgroup; *total = the workgroup's sum
-__device__ __forceinline__ int4 block_scan4(int4 v, int4* total) {
-    __shared__ int4 wsum[4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int4 inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int4 o = shfl_up4(inc, d);
-        if (lane >= d) inc = add4(inc, o);
-    }
-    if (lane == 63) wsum[wv] = inc;
-    __syncthreads();
-    int4 base = make_int4(0, 0, 0, 0), tot = make_int4(0, 0, 0, 0);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (i < wv) base = add4(base, wsum[i]);
-        tot = add4(tot, wsum[i]);
-    }
-    *total = tot;
-    __syncthreads();
-    return make_int4(base.x + inc.x - v.x, base.y + inc.y - v.y, base.z + inc.z - v.z, base.w + inc.w - v.w);
-}
 
 __global__ __launch_bounds__(256) void k_rank_scan_sums(int n, RankWs w) {
     const int r0 = blockIdx.x * SCAN_ROWS + threadIdx.x * 4;
     int4 t = make_int4(0, 0, 0, 0);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) t = add4(t, scan_vals(w, r0 + i, n));
+    for (int i = 0; i < 4; ++i) t = t + scan_vals(w, r0 + i, n);
     int4 total;
-    block_scan4(t, &total);
+    block_scan(t, &total);
     if (threadIdx.x == 0) w.bsum[blockIdx.x] = total;
 }
 
 // one workgroup: block sums -> exclusive prefixes (in place), totals -> hdr and status
 __global__ __launch_bounds__(256) void k_rank_scan_top(int nb, RankWs w, int max_queries, int* status) {
-    const int per = (nb + 255) / 256, b0 = threadIdx.x * per;
-    int4 t = make_int4(0, 0, 0, 0);
-    for (int i = b0; i < b0 + per && i < nb; ++i) t = add4(t, w.bsum[i]);
-    int4 total;
-    int4 run = block_scan4(t, &total);
-    for (int i = b0; i < b0 + per && i < nb; ++i) {
-        const int4 v = w.bsum[i];
-        w.bsum[i] = run;
-        run = add4(run, v);
-    }
+    const int4 total = scan_top(w.bsum, nb);
     if (threadIdx.x == 0) {
         w.hdr[0] = total.x; w.hdr[1] = total.y; w.hdr[2] = total.z; w.hdr[3] = total.w;
         status[0] = total.x + total.y; status[1] = total.x; status[3] = total.w;
@@ -207,9 +171,9 @@ __global__ __launch_bounds__(256) void k_rank_scan_apply(const long long* qid, i
     int4 v[4];
     int4 t = make_int4(0, 0, 0, 0);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) { v[i] = scan_vals(w, r0 + i, n); t = add4(t, v[i]); }
+    for (int i = 0; i < 4; ++i) { v[i] = scan_vals(w, r0 + i, n); t = t + v[i]; }
     int4 total;
-    int4 pre = add4(block_scan4(t, &total), w.bsum[blockIdx.x]);
+    int4 pre = block_scan(t, &total) + w.bsum[blockIdx.x];
     const int n_ge5 = w.hdr[0];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -222,20 +186,12 @@ __global__ __launch_bounds__(256) void k_rank_scan_apply(const long long* qid, i
                 if (pos < max_queries) out_query[pos] = qid[r0 + i];
             }
         }
-        pre = add4(pre, v[i]);
+        pre = pre + v[i];
     }
 }
 
 __global__ __launch_bounds__(256) void k_rank_scatter(int n, RankWs w) {
-    const int r = blockIdx.x * 256 + threadIdx.x;
-    const int qs = r < n ? w.qslot[r] : -1;
-    const bool live = qs >= 0;
-    const Run run = wave_run((long long)qs, live);
-    const int lane = threadIdx.x & 63;
-    int base = 0;
-    if (live && lane == run.head) base = w.qoff[qs] + atomicAdd(&w.qfill[qs], run.len);
-    base = __shfl(base, run.head);
-    if (live) w.qlist[base + lane - run.head] = r;        // offsets + fills stay below the query's row count: inside [0, n)
+    scatter_rows(n, w.qslot, w.qoff, w.qfill, w.qlist);
 }
 
 // one wavefront per output row, wavefronts stride over the rows (the row count is known on the device only)
@@ -248,27 +204,15 @@ __global__ __launch_bounds__(256) void k_rank_select(const long long* pid, RankW
         const int qs = w.qsel[o];
         const int cnt = w.qcnt[qs], off = w.qoff[qs];
         const bool filtered = w.qsurv[qs] >= 5;
-        u64 pe = ~0ull;                                   // previous pick: every image is below ~0
-        int pr = -1, picked = 0;
+        Pick prev{~0ull, 0};                              // previous pick: every image is below ~0
+        int picked = 0;
         for (int k = 0; k < 5; ++k) {
-            u64 be = 0;                                   // no image is 0
-            int br = 0x7FFFFFFF;
-            for (int i = lane; i < cnt; i += 64) {
+            const Pick b = wave_next(cnt, prev, [&](int i) {             // (image descending, row ascending) over the survivors / all rows
                 const int r = w.qlist[off + i];
-                if (filtered && !w.surv[r]) continue;
-                const u64 e = w.enc[r];
-                if (!(e < pe || (e == pe && r > pr))) continue;          // after the previous pick in (image descending, row ascending)
-                if (e > be || (e == be && r < br)) { be = e; br = r; }
-            }
-#pragma unroll
-            for (int d = 32; d >= 1; d >>= 1) {
-                const u64 oe = __shfl_xor(be, d);
-                const int orr = __shfl_xor(br, d);
-                if (oe > be || (oe == be && orr < br)) { be = oe; br = orr; }
-            }
-            long long prod = -1;
-            if (be != 0) { prod = pid[br]; pe = be; pr = br; ++picked; }
-            else pe = 0;                                  // exhausted: nothing is below image 0, the remaining rounds write -1
+                return Pick{filtered && !w.surv[r] ? 0 : w.enc[r], (unsigned)r};
+            });
+            long long prod = -1;                          // exhausted: prev stays, so the remaining rounds find nothing either and write -1
+            if (b.img != 0) { prod = pid[b.tie]; prev = b; ++picked; }
             if (lane == 0) out_products[(long long)o * 5 + k] = prod;
         }
         if (lane == 0) out_count[o] = picked;

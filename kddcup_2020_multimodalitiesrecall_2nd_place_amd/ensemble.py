@@ -141,23 +141,12 @@ def rank_device(query_id, product_id, score, gap=GAP, tie=TIE):
     -> (out_query [m] int64, out_products [m, 5] int64 (-1: unused), out_count [m] int32, status [4] int32), device tensors with
     m = the row count (always enough room); status = (output rows, rows of the >= 5-survivor class -- they come first --, flags, distinct queries).
     Only enqueues on the current stream: nothing is read back, nothing waits."""
-    import numpy as np
     import torch
 
     from . import lib as _lib
-    dev = next((t.device for t in (score, query_id, product_id) if torch.is_tensor(t) and t.is_cuda), torch.device("cuda", torch.cuda.current_device()))
-
-    def up(x, dtypes):
-        t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
-        if t.dtype not in dtypes:
-            t = t.to(dtypes[0])
-        return t.to(dev, non_blocking=True).contiguous().reshape(-1)
-
-    q, p = up(query_id, (torch.int64,)), up(product_id, (torch.int64,))
-    s = up(score, (torch.float64, torch.float32))
+    from .ndcg import _check_rc, _ptr, _rows_on_device, _score_ptrs
+    (s, q, p), dev = _rows_on_device((score, query_id, product_id), ((torch.float64, torch.float32), (torch.int64,), (torch.int64,)), "rank_device")
     n = s.shape[0]
-    if q.shape[0] != n or p.shape[0] != n:
-        raise ValueError("rank_device: %d query ids, %d product ids, %d scores" % (q.shape[0], p.shape[0], n))
     l = _lib.load()
     ws_bytes = l.mms_rank_workspace_bytes(n)
     if ws_bytes < 0:
@@ -168,14 +157,9 @@ def rank_device(query_id, product_id, score, gap=GAP, tie=TIE):
     out_products = torch.empty((m, 5), dtype=torch.int64, device=dev)
     out_count = torch.empty((m,), dtype=torch.int32, device=dev)
     status = torch.empty((4,), dtype=torch.int32, device=dev)
-    ptr = lambda t: t.data_ptr() if t.numel() else None
-    f32 = s.dtype == torch.float32
-    # a non-NULL score pointer even for n == 0 (exactly one of the two must be given); never dereferenced then
-    sp = ptr(s) or status.data_ptr()
-    rc = l.mms_rank_submission(ptr(q), ptr(p), sp if f32 else None, None if f32 else sp, n, float(gap), float(tie), ws.data_ptr(), ws_bytes, m,
-                               ptr(out_query), ptr(out_products), ptr(out_count), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    if rc != 0:
-        raise _lib.MmsError("mms_rank_submission failed (%d): %s" % (rc, l.mms_global_error().decode()))
+    rc = l.mms_rank_submission(_ptr(q), _ptr(p), *_score_ptrs(s, status), n, float(gap), float(tie), ws.data_ptr(), ws_bytes, m,
+                               _ptr(out_query), _ptr(out_products), _ptr(out_count), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    _check_rc(l, rc, "mms_rank_submission")
     return out_query, out_products, out_count, status
 
 
@@ -243,6 +227,30 @@ def weight_grid(members: int = 4, steps: int = 20):
     return np.array(rows, np.float64) / steps
 
 
+def _fit(device_call, host_call, use_device, info):
+    """The common half of ``fit_weights`` / ``fit_filter``: the values of every grid row -- from ``device_call() -> (values, _, status)`` with ONE
+    synchronising read when ``use_device`` and the device raises no flag but "missing", else from ``host_call(to_np) -> values`` -- and the FIRST row
+    that attains the maximum.  -> (index, values)."""
+    import numpy as np
+
+    from . import ndcg
+    values, flags = None, 0
+    if use_device:
+        import torch
+        dvalues, _, status = device_call()
+        host = torch.cat([status.to(torch.float64), dvalues]).cpu().numpy()      # the one synchronising read
+        flags = int(host[2])
+        if flags & ~ndcg.FLAG_MISSING_QUERY == 0:
+            if flags & ndcg.FLAG_MISSING_QUERY:                                  # only without allow_missing
+                raise KeyError("%d key queries have no rows" % int(host[3]))
+            values = host[4:].copy()
+    if info is not None:
+        info.update(path="device" if values is not None else "host", flags=flags)
+    if values is None:
+        values = host_call(lambda x: x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x))
+    return int(np.argmax(values)), values                                        # the first row that attains the maximum
+
+
 def fit_weights(query_id, product_id, members, rank_label, grid=None, k: int = 5, allow_missing: bool = False, where: str = "device", info: dict = None):
     """The ensemble weights as a result of the valid set: nDCG@k of the merge ``(...(w0 * s0 + w1 * s1) + ...)`` (``ndcg.merge_members``: IEEE double,
     every operation rounded on its own, main.py:59's evaluation) for every row ``w`` of ``grid`` (default ``weight_grid(M, 20)``), and the winner --
@@ -262,23 +270,13 @@ def fit_weights(query_id, product_id, members, rank_label, grid=None, k: int = 5
     grid = weight_grid(M, 20) if grid is None else np.ascontiguousarray(grid, np.float64)
     if grid.ndim != 2 or grid.shape[0] == 0:
         raise ValueError("fit_weights: the grid must be [W >= 1, %d]" % M)
-    values, flags = None, 0
-    if where == "device" and len(label_dict):
-        import torch
-        dvalues, _, status = ndcg.ndcg_sweep_device(query_id, product_id, members, grid, rank_label, k, allow_missing)
-        host = torch.cat([status.to(torch.float64), dvalues]).cpu().numpy()      # the one synchronising read
-        flags = int(host[2])
-        if flags & ~ndcg.FLAG_MISSING_QUERY == 0:
-            if flags & ndcg.FLAG_MISSING_QUERY:                                  # only without allow_missing
-                raise KeyError("%d key queries have no rows" % int(host[3]))
-            values = host[4:].copy()
-    if info is not None:
-        info.update(path="device" if values is not None else "host", flags=flags)
-    if values is None:
-        to_np = lambda x: x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+
+    def host_call(to_np):
         mem = np.stack([to_np(m) for m in members]) if isinstance(members, (list, tuple)) else to_np(members)
-        values, _ = ndcg.ndcg_sweep_host(to_np(query_id), to_np(product_id), mem, grid, label_dict, k, allow_missing)
-    index = int(np.argmax(values))                                               # the first row that attains the maximum
+        return ndcg.ndcg_sweep_host(to_np(query_id), to_np(product_id), mem, grid, label_dict, k, allow_missing)[0]
+
+    index, values = _fit(lambda: ndcg.ndcg_sweep_device(query_id, product_id, members, grid, rank_label, k, allow_missing), host_call,
+                         where == "device" and len(label_dict), info)
     return tuple(float(x) for x in grid[index]), float(values[index]), index, values
 
 
@@ -312,20 +310,7 @@ def fit_filter(query_id, product_id, score, rank_label, filters=None, k: int = 5
     filters = filter_grid() if filters is None else np.ascontiguousarray(filters, np.float64)
     if filters.ndim != 2 or filters.shape[1] != 2 or filters.shape[0] == 0:
         raise ValueError("fit_filter: the filters must be [G >= 1, 2] rows of (gap, tie)")
-    values, flags = None, 0
-    if where == "device" and len(label_dict):
-        import torch
-        dvalues, _, status = ndcg.filter_sweep_device(query_id, product_id, score, filters, rank_label, k, allow_missing)
-        host = torch.cat([status.to(torch.float64), dvalues]).cpu().numpy()      # the one synchronising read
-        flags = int(host[2])
-        if flags & ~ndcg.FLAG_MISSING_QUERY == 0:
-            if flags & ndcg.FLAG_MISSING_QUERY:                                  # only without allow_missing
-                raise KeyError("%d key queries have no rows" % int(host[3]))
-            values = host[4:].copy()
-    if info is not None:
-        info.update(path="device" if values is not None else "host", flags=flags)
-    if values is None:
-        to_np = lambda x: x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
-        values, _, _ = ndcg.filter_sweep_host(to_np(query_id), to_np(product_id), to_np(score), filters, label_dict, k, allow_missing)
-    index = int(np.argmax(values))                                               # the first row that attains the maximum
+    index, values = _fit(lambda: ndcg.filter_sweep_device(query_id, product_id, score, filters, rank_label, k, allow_missing),
+                         lambda to_np: ndcg.filter_sweep_host(to_np(query_id), to_np(product_id), to_np(score), filters, label_dict, k, allow_missing)[0],
+                         where == "device" and len(label_dict), info)
     return (float(filters[index, 0]), float(filters[index, 1])), float(values[index]), index, values

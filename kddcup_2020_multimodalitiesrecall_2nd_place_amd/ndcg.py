@@ -161,9 +161,9 @@ def _rows_on_device(arrays, dtypes, what):
     return out, dev
 
 
-def _workspace(l, n, key, dev, what):
+def _workspace(ws_bytes, n, key, dev, what):
+    """The workspace of ``ws_bytes`` (what a ``mms_*_workspace_bytes`` returned: negative for a table beyond the limits) -> (tensor, ws_bytes)."""
     import torch
-    ws_bytes = l.mms_ndcg_workspace_bytes(n, key.n_queries, key.n_products)
     if ws_bytes < 0:
         raise ValueError("%s: %d rows, %d key queries, %d key products: the device path takes at most 2^22 rows / key products and 2^20 key queries"
                          % (what, n, key.n_queries, key.n_products))
@@ -171,6 +171,19 @@ def _workspace(l, n, key, dev, what):
 
 
 _ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+
+
+def _score_ptrs(s, status):
+    """-> (score_f32, score_f64) of an entry point that takes exactly one of the two: a non-NULL pointer even for n == 0 (never dereferenced then)."""
+    import torch
+    sp = _ptr(s) or status.data_ptr()
+    return (sp, None) if s.dtype == torch.float32 else (None, sp)
+
+
+def _check_rc(l, rc, name):
+    if rc != 0:
+        from . import lib as _lib
+        raise _lib.MmsError("%s failed (%d): %s" % (name, rc, l.mms_global_error().decode()))
 
 
 def relevance_device(query_id, product_id, rank_label, status_out: list = None):
@@ -184,13 +197,12 @@ def relevance_device(query_id, product_id, rank_label, status_out: list = None):
     key = _key_on(rank_label, dev)
     n = q.shape[0]
     l = _lib.load()
-    ws, ws_bytes = _workspace(l, n, key, dev, "relevance_device")
+    ws, ws_bytes = _workspace(l.mms_ndcg_workspace_bytes(n, key.n_queries, key.n_products), n, key, dev, "relevance_device")
     labels = torch.empty((n,), dtype=torch.int64, device=dev)
     status = torch.empty((4,), dtype=torch.int32, device=dev)
     rc = l.mms_key_relevance(_ptr(q), _ptr(p), n, _ptr(key.key_query), _ptr(key.key_off), _ptr(key.key_product), key.n_queries, key.n_products,
                              ws.data_ptr(), ws_bytes, _ptr(labels), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    if rc != 0:
-        raise _lib.MmsError("mms_key_relevance failed (%d): %s" % (rc, l.mms_global_error().decode()))
+    _check_rc(l, rc, "mms_key_relevance")
     if status_out is not None:
         status_out.append(status)
     return labels
@@ -209,18 +221,15 @@ def ndcg_codes_device(query_id, product_id, score, rank_label, k: int = 5, allow
     key = _key_on(rank_label, dev)
     n = s.shape[0]
     l = _lib.load()
-    ws, ws_bytes = _workspace(l, n, key, dev, "ndcg_device")
+    ws, ws_bytes = _workspace(l.mms_ndcg_workspace_bytes(n, key.n_queries, key.n_products), n, key, dev, "ndcg_device")
     codes = torch.empty((key.n_queries,), dtype=torch.int32, device=dev)
     topk = torch.empty((key.n_queries, k), dtype=torch.int64, device=dev) if want_topk else None
     hist = torch.empty(((k + 1) << k,), dtype=torch.int64, device=dev)
     status = torch.empty((4,), dtype=torch.int32, device=dev)
-    f32 = s.dtype == torch.float32
-    sp = _ptr(s) or status.data_ptr()        # a non-NULL score pointer even for n == 0 (exactly one of the two must be given); never dereferenced then
-    rc = l.mms_ndcg_at_k(_ptr(q), _ptr(p), sp if f32 else None, None if f32 else sp, n, _ptr(key.key_query), _ptr(key.key_off), _ptr(key.key_product),
+    rc = l.mms_ndcg_at_k(_ptr(q), _ptr(p), *_score_ptrs(s, status), n, _ptr(key.key_query), _ptr(key.key_off), _ptr(key.key_product),
                          key.n_queries, key.n_products, k, int(bool(allow_missing)), ws.data_ptr(), ws_bytes, _ptr(codes), _ptr(topk), hist.data_ptr(),
                          status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    if rc != 0:
-        raise _lib.MmsError("mms_ndcg_at_k failed (%d): %s" % (rc, l.mms_global_error().decode()))
+    _check_rc(l, rc, "mms_ndcg_at_k")
     return codes, topk, hist, status
 
 
@@ -263,6 +272,14 @@ def ndcg_device(query_id, product_id, score, rank_label, k: int = 5, info: dict 
 # ---- weight sweep: the histogram and the value of EVERY weight vector of a grid (mms_ndcg_weight_sweep, csrc/ndcg_sweep.hip) ----
 MAX_MEMBERS, MAX_WEIGHTS = 8, 1 << 20                                                      # MMS_SWEEP_MAX_MEMBERS, MMS_SWEEP_MAX_WEIGHTS
 _BIN_TABLES: dict = {}
+
+
+def _bin_table(k, dev):
+    """``bin_values(k)`` on the device ``dev``."""
+    import torch
+    if (k, dev) not in _BIN_TABLES:
+        _BIN_TABLES[k, dev] = torch.from_numpy(bin_values(k).copy()).to(dev)
+    return _BIN_TABLES[k, dev]
 
 
 def bin_values(k: int = 5):
@@ -337,22 +354,15 @@ def ndcg_sweep_device(query_id, product_id, members, weights, rank_label, k: int
     if key.n_queries == 0:
         raise ValueError("ndcg_sweep_device: empty answer key")
     l = _lib.load()
-    ws_bytes = l.mms_ndcg_sweep_workspace_bytes(n, key.n_queries, key.n_products, M)
-    if ws_bytes < 0:
-        raise ValueError("ndcg_sweep_device: %d rows, %d key queries, %d key products: the device path takes at most 2^22 rows / key products and 2^20 "
-                         "key queries" % (n, key.n_queries, key.n_products))
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    if (k, dev) not in _BIN_TABLES:
-        _BIN_TABLES[k, dev] = torch.from_numpy(bin_values(k).copy()).to(dev)
-    table = _BIN_TABLES[k, dev]
+    ws, ws_bytes = _workspace(l.mms_ndcg_sweep_workspace_bytes(n, key.n_queries, key.n_products, M), n, key, dev, "ndcg_sweep_device")
+    table = _bin_table(k, dev)
     hist = torch.empty((W, (k + 1) << k), dtype=torch.int64, device=dev)
     values = torch.empty((W,), dtype=torch.float64, device=dev)
     status = torch.empty((4,), dtype=torch.int32, device=dev)
     rc = l.mms_ndcg_weight_sweep(_ptr(q), _ptr(p), _ptr(mem), M, n, _ptr(key.key_query), _ptr(key.key_off), _ptr(key.key_product), key.n_queries,
                                  key.n_products, _ptr(wts), W, k, int(bool(allow_missing)), table.data_ptr(), key.n_queries, ws.data_ptr(), ws_bytes,
                                  _ptr(hist), _ptr(values), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    if rc != 0:
-        raise _lib.MmsError("mms_ndcg_weight_sweep failed (%d): %s" % (rc, l.mms_global_error().decode()))
+    _check_rc(l, rc, "mms_ndcg_weight_sweep")
     return values, hist, status
 
 
@@ -449,23 +459,14 @@ def filter_sweep_device(query_id, product_id, score, filters, rank_label, k: int
         raise ValueError("filter_sweep_device: empty answer key")
     n, G = s.shape[0], flt.shape[0]
     l = _lib.load()
-    ws_bytes = l.mms_filter_sweep_workspace_bytes(n, key.n_queries, key.n_products)
-    if ws_bytes < 0:
-        raise ValueError("filter_sweep_device: %d rows, %d key queries, %d key products: the device path takes at most 2^22 rows / key products and 2^20 "
-                         "key queries" % (n, key.n_queries, key.n_products))
-    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)             # (the caching allocator returns 512-byte aligned blocks)
-    if (k, dev) not in _BIN_TABLES:
-        _BIN_TABLES[k, dev] = torch.from_numpy(bin_values(k).copy()).to(dev)
-    table = _BIN_TABLES[k, dev]
+    ws, ws_bytes = _workspace(l.mms_filter_sweep_workspace_bytes(n, key.n_queries, key.n_products), n, key, dev, "filter_sweep_device")
+    table = _bin_table(k, dev)
     hist = torch.empty((G, (k + 1) << k), dtype=torch.int64, device=dev)
     values = torch.empty((G,), dtype=torch.float64, device=dev)
     codes = torch.empty((G, key.n_queries), dtype=torch.int32, device=dev) if want_codes else None
     status = torch.empty((4,), dtype=torch.int32, device=dev)
-    f32 = s.dtype == torch.float32
-    sp = _ptr(s) or status.data_ptr()        # a non-NULL score pointer even for n == 0 (exactly one of the two must be given); never dereferenced then
-    rc = l.mms_filter_sweep(_ptr(q), _ptr(p), sp if f32 else None, None if f32 else sp, n, _ptr(key.key_query), _ptr(key.key_off), _ptr(key.key_product),
+    rc = l.mms_filter_sweep(_ptr(q), _ptr(p), *_score_ptrs(s, status), n, _ptr(key.key_query), _ptr(key.key_off), _ptr(key.key_product),
                             key.n_queries, key.n_products, _ptr(flt), G, k, int(bool(allow_missing)), table.data_ptr(), key.n_queries, ws.data_ptr(), ws_bytes,
                             _ptr(hist), _ptr(values), _ptr(codes), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    if rc != 0:
-        raise _lib.MmsError("mms_filter_sweep failed (%d): %s" % (rc, l.mms_global_error().decode()))
+    _check_rc(l, rc, "mms_filter_sweep")
     return (values, hist, status, codes) if want_codes else (values, hist, status)

@@ -271,6 +271,16 @@ def _answer_labels(key):
     return hook
 
 
+def _relabel(labels, rank_label, device, fed=True):
+    """-> (rank_label, relabel): with ``labels == "answer"`` (and a model that is ``fed`` labels) the key as an ``ndcg.AnswerKey`` on ``device`` and
+    the ``_answer_labels`` hook on it; otherwise the key as it came and no hook."""
+    from . import ndcg
+    if labels != "answer" or not fed:
+        return rank_label, None
+    key = rank_label if isinstance(rank_label, ndcg.AnswerKey) else ndcg.AnswerKey(rank_label, device)
+    return key, _answer_labels(key)
+
+
 def _model_pass(scorer, tsv_path, vocab_path, label_table, sen2forest, batch_pairs, threads, ramp, shard, shard_by, stats, feat_decode, relabel=None):
     """The overlapped pass of ``stream_scores_tsv`` with the scores left on the device: -> (query_id, product_id, [softmax(logit)[:, 1] per batch],
     counts).  ``relabel`` (``_answer_labels``): the batch's ids travel to the device with it and the hook rewrites the device feed before scoring."""
@@ -337,12 +347,8 @@ def evaluate_tsv_native(scorer, tsv_path, vocab_path, label_table, rank_label, k
     ``shard = (rank, world)``: this rank's rows only; the result is ``(histogram, key queries evaluated)`` for ``sharding.reduce_ndcg`` +
     ``ndcg.ndcg_from_hist`` instead of the float.  ``info`` receives the metric's ``{"path", "flags"}``; ``scores_out`` (a dict) receives
     ``query_id`` / ``product_id`` (numpy) and ``score`` (device fp32)."""
-    from . import ndcg
     _check_eval_args(metric, labels)
-    relabel = None
-    if labels == "answer" and scorer.cfg.name == "zk":
-        rank_label = rank_label if isinstance(rank_label, ndcg.AnswerKey) else ndcg.AnswerKey(rank_label, scorer.device)
-        relabel = _answer_labels(rank_label)
+    rank_label, relabel = _relabel(labels, rank_label, scorer.device, scorer.cfg.name == "zk")
     qid, pid, probs, _ = _model_pass(scorer, tsv_path, vocab_path, label_table, sen2forest, batch_pairs, threads, ramp, shard, shard_by, stats,
                                      feat_decode, relabel)
     score = torch.cat(probs).float() if probs else torch.zeros(0, dtype=torch.float32, device=scorer.device)
@@ -452,12 +458,8 @@ class EnsembleScorer:
         the pass of ``score_tsv_native`` with the merged scores left on the device, the zk members' label feed from the answer key
         (``labels="answer"``) or all ones (``labels="ones"``, today's feed), the metric on the GPU (``metric="device"``) or by
         ``ndcg.ndcg_from_arrays`` on the fp64 copy of the scores (``metric="host"``) -- the same float."""
-        from . import ndcg
         _check_eval_args(metric, labels)
-        relabel = None
-        if labels == "answer":
-            rank_label = rank_label if isinstance(rank_label, ndcg.AnswerKey) else ndcg.AnswerKey(rank_label, self.zk.device)
-            relabel = _answer_labels(rank_label)
+        rank_label, relabel = _relabel(labels, rank_label, self.zk.device)
         qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=False, relabel=relabel)
         score = torch.cat([m for m, _ in out]).double() if out else torch.zeros(0, dtype=torch.float64, device=self.zk.device)
         if scores_out is not None:
@@ -473,12 +475,9 @@ class EnsembleScorer:
         in ``evaluate_tsv_native``.  ``scores_out`` (a dict) receives ``query_id`` / ``product_id`` (numpy) and ``members`` (device fp32 [4, n]).
         The value of a weight vector is that of main.py's DOUBLE merge of the fp32 member scores; ``evaluate_tsv_native`` ranks the fp32 merge
         of the fused call, which can differ on a near tie."""
-        from . import ensemble, ndcg
+        from . import ensemble
         _check_eval_args("device", labels)
-        relabel = None
-        if labels == "answer":
-            rank_label = rank_label if isinstance(rank_label, ndcg.AnswerKey) else ndcg.AnswerKey(rank_label, self.zk.device)
-            relabel = _answer_labels(rank_label)
+        rank_label, relabel = _relabel(labels, rank_label, self.zk.device)
         qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=True, relabel=relabel)
         mem = torch.cat([m for _, m in out], 1) if out else torch.zeros((4, 0), dtype=torch.float32, device=self.zk.device)
         if scores_out is not None:
@@ -492,12 +491,9 @@ class EnsembleScorer:
         ``filters`` (default ``ensemble.filter_grid()``, 102 rows) on the fp64 copy of the merged scores in one library call (``mms_filter_sweep``).
         -> ((gap, tie), value, index, values numpy [G]), the tuple of ``fit_filter``; pass the winner to ``submission_tsv_native(gap=, tie=)``.
         ``scores_out`` (a dict) receives ``query_id`` / ``product_id`` (numpy) and ``score`` (device fp64)."""
-        from . import ensemble, ndcg
+        from . import ensemble
         _check_eval_args("device", labels)
-        relabel = None
-        if labels == "answer":
-            rank_label = rank_label if isinstance(rank_label, ndcg.AnswerKey) else ndcg.AnswerKey(rank_label, self.zk.device)
-            relabel = _answer_labels(rank_label)
+        rank_label, relabel = _relabel(labels, rank_label, self.zk.device)
         qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=False, relabel=relabel)
         score = torch.cat([m for m, _ in out]).double() if out else torch.zeros(0, dtype=torch.float64, device=self.zk.device)
         if scores_out is not None:

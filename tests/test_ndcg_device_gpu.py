@@ -97,6 +97,23 @@ def test_key_length_edges_of_the_scan_block(qa):
     _check(q, p, s, key, 8)
 
 
+def test_262145_key_queries_take_two_block_sums_per_thread_of_the_scan_top():
+    """257 scan blocks of 1 024 key queries: the one workgroup that turns the block sums into prefixes owns two of them per thread.  One row per key
+    query in shuffled order, so a wrong list offset hands a query another query's row: its relevance bit in the code differs."""
+    qa = 256 * 1024 + 1
+    rng = np.random.default_rng(262145)
+    perm = rng.permutation(qa)
+    q, p = (1000 + np.arange(qa, dtype=np.int64))[perm], rng.integers(1, 3, qa).astype(np.int64)[perm]
+    s = (rng.integers(0, 5, qa) * 0.25).astype(np.float64)
+    key = {int(1000 + i): [int(t)] for i, t in enumerate(rng.integers(1, 3, qa))}
+    want = ndcg.ndcg_codes(q, p, s, key, 1)
+    assert 0 < int((want & 1).sum()) < qa
+    codes, _, hist, status = _device_all(q, p, s, key, 1)
+    assert status.tolist() == [qa, qa, 0, 0]
+    assert np.array_equal(codes, want)
+    assert np.array_equal(hist, ndcg.hist_from_codes(want, 1))
+
+
 def test_one_query_of_300_rows_loops_over_its_list():
     q, p, s, key = _plain_table([300, 7, 64, 65, 128, 129], 81)
     _check(q, p, s, key, 5)

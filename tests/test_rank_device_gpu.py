@@ -316,6 +316,14 @@ def test_240000_rows_fp32():
     assert len(want) > 1000
 
 
+def test_262170_rows_take_two_block_sums_per_thread_of_the_scan_top():
+    """257 scan blocks of 1 024 rows: the one workgroup that turns the block sums into prefixes owns two of them per thread"""
+    q, p, s = _big_table(seed=22, nq=8739)
+    assert len(q) == 262170 > 256 * 1024
+    want = _check(q, p, s)
+    assert len(want) > 1000
+
+
 # ---- 6. determinism -----------------------------------------------------------------------------------------------------------------------------------
 def _raw_bytes(q, p, s):
     oq, op, oc, st = ensemble.rank_device(q, p, s)
