@@ -174,11 +174,11 @@ typedef struct mms_ensemble_batch {
 /* ABI revision of the structs and entry points declared in this header.  It changes whenever a struct gains a field or an entry
  * point changes its signature (r1: 1; r2 added mms_config.fuse_layernorm, mms_zk_batch.label_ids, mms_lxmert_batch.label_ids / x_norm
  * without bumping it; r3: 3, then 4 with mms_config.fuse_attention; r4: 5 -- mms_dbg_gemm takes the engine per call,
- * the process-global mms_set_gemm_variant and the lab engines' hooks left the product library, fuse_layernorm became a mask; r5: 6 -- mms_dbg_qkv_attn and mms_side_lane_flops added; r7: 7 -- mms_decode_feats_b64 added; r8: 8 -- mms_rank_workspace_bytes and mms_rank_submission added; r9: 9 -- mms_ndcg_workspace_bytes, mms_key_relevance and mms_ndcg_at_k added; r10: 10 -- mms_ndcg_sweep_workspace_bytes and mms_ndcg_weight_sweep added; r11: 11 -- mms_filter_sweep_workspace_bytes and mms_filter_sweep added).  A caller built against another revision would make the library read past its structs, so compare
+ * the process-global mms_set_gemm_variant and the lab engines' hooks left the product library, fuse_layernorm became a mask; r5: 6 -- mms_dbg_qkv_attn and mms_side_lane_flops added; r7: 7 -- mms_decode_feats_b64 added; r8: 8 -- mms_rank_workspace_bytes and mms_rank_submission added; r9: 9 -- mms_ndcg_workspace_bytes, mms_key_relevance and mms_ndcg_at_k added; r10: 10 -- mms_ndcg_sweep_workspace_bytes and mms_ndcg_weight_sweep added; r11: 11 -- mms_filter_sweep_workspace_bytes and mms_filter_sweep added; r12: 12 -- mms_joint_sweep_workspace_bytes and mms_joint_sweep added).  A caller built against another revision would make the library read past its structs, so compare
  * BEFORE the first mms_create:  if (mms_version() != MMS_ABI_VERSION) abort();   (lib.py's load() does) */
-#define MMS_ABI_VERSION 11
+#define MMS_ABI_VERSION 12
 int mms_version(void);
-const char* mms_global_error(void);              /* message of the last failing mms_create / mms_decode_feats_b64 / mms_rank_submission / mms_key_relevance / mms_ndcg_at_k / mms_ndcg_weight_sweep / mms_filter_sweep */
+const char* mms_global_error(void);              /* message of the last failing mms_create / mms_decode_feats_b64 / mms_rank_submission / mms_key_relevance / mms_ndcg_at_k / mms_ndcg_weight_sweep / mms_filter_sweep / mms_joint_sweep */
 
 int mms_create(const mms_config* cfg, mms_handle** out);
 void mms_destroy(mms_handle* h);
@@ -417,6 +417,48 @@ int mms_filter_sweep(const int64_t* query_id, const int64_t* product_id, const f
                      void* workspace, int64_t workspace_bytes, int64_t* hist_out /* [n_filters][(k+1)<<k], zeroed by the call */,
                      double* value_out /* [n_filters] or NULL; needs bin_value */, int32_t* code_out /* [n_filters][n_key_queries] or NULL */,
                      int32_t* status /* [4] as mms_ndcg_at_k */, void* stream);
+
+/* Fitting the ensemble weights and the uniqueness filter JOINTLY on the valid set: the nDCG@k histogram -- and, optionally, the value -- of the
+ * SUBMISSION rows for EVERY (weight vector, filter) pair of two grids in one call.  Rows, answer key, allow_missing and status words are those of
+ * mms_ndcg_at_k; members / n_members / weights are those of mms_ndcg_weight_sweep, filters / k those of mms_filter_sweep.
+ *   ARITHMETIC CONTRACT: none of its own.  It composes the two existing contracts: item (v, g) -- hist_out[v][g], value_out[v][g] -- is by
+ *   definition what mms_filter_sweep yields for filter g on score_f64 = score_v, the merge of mms_ndcg_weight_sweep for weight vector v (IEEE
+ *   double, members widened exactly, every product and every sum rounded on its own, left to right, never a fused multiply-add).  So d, keep,
+ *   survive, the >= 5 / 1..4 / 0 survivor cases, the order (score descending, then row ascending), -0.0 == +0.0, NaN / +-inf filters and the
+ *   divisor n_key_queries_total are mms_filter_sweep's, unchanged: ndcg.joint_sweep_host on the host.  The product statistics (best, second) depend
+ *   on the weights and are formed per weight vector.
+ *   flags (status[2]): those of mms_filter_sweep.  Bit 1: a non-finite merged score in ANY row for ANY weight vector (or a non-finite first
+ *   member); bit 4: a repeated (query, product) pair.  With a non-zero flag word (other than bit 0 under allow_missing, never set then) the
+ *   outputs are unspecified, but nothing is written outside them or outside the workspace.
+ *   hist_out may be NULL: only values are written, and the histograms of the vectors in flight live in the workspace (the full array is
+ *   n_weights * n_filters * ((k + 1) << k) * 8 bytes: about 280 MB at 1 771 x 102, k = 5).  value_out may be NULL; given, it needs bin_value and
+ *   n_key_queries_total >= 1.
+ *   workspace: device memory, 256-byte aligned.  The weight vectors are processed in tiles of 64, and the tiles in CHUNKS, because the per-vector
+ *   product statistics take 16 B x 64 x n per tile: mms_joint_sweep_workspace_bytes(n, n_key_queries, n_key_products, n_members, tiles_per_chunk)
+ *   is the size for chunks of tiles_per_chunk tiles WITH hist_out; without hist_out add tiles_per_chunk * 64 * n_filters * ((k + 1) << k) * 8
+ *   bytes, rounded up to a multiple of 256 per tile.  The call derives its chunk from workspace_bytes -- as many tiles as fit, one at least -- and
+ *   the results do not depend on it.
+ * Once per call: the score-independent stages of mms_ndcg_at_k, the product table of mms_rank_submission, the rows grouped by product and by key
+ * query.  Per chunk: the product statistics per weight vector, the unfiltered top-k per (key query, vector), then a wavefront takes a tile of 64
+ * weight vectors, ONE filter and a slab of key queries, a lane owning one vector (csrc/joint_sweep.hip).  Integer atomics only: equal inputs give
+ * bit-equal outputs.  No kernel waits on another workgroup.  ONLY ENQUEUES on `stream` (fills and kernels): no allocation, no synchronisation, no
+ * device -> host read.  Handle-free.
+ * Returns MMS_ERR_ARG (message in mms_global_error naming the function, nothing launched) for a count that is negative or over its cap (those of
+ * mms_ndcg_at_k; n_members in 1..MMS_SWEEP_MAX_MEMBERS, n_filters <= MMS_FILTER_MAX, n_weights and n_weights * n_filters <= MMS_JOINT_MAX_ITEMS), k
+ * outside 1..MMS_FILTER_MAX_K, a NULL pointer whose count is non-zero (status: always; hist_out and value_out may be NULL), key products without
+ * key queries, value_out without bin_value or with n_key_queries_total < 1, a workspace that is not 256-byte aligned or too small for a chunk of
+ * ONE tile (needed when n_key_queries > 0; with n_weights == 0 or n_filters == 0 the part that does not grow with tiles_per_chunk is enough).
+ * n == 0, n_key_queries == 0: zero histograms and values, status as mms_filter_sweep; n_weights == 0 or n_filters == 0: the status alone. */
+#define MMS_JOINT_MAX_ITEMS (1 << 22)
+int64_t mms_joint_sweep_workspace_bytes(int64_t n, int64_t n_key_queries, int64_t n_key_products, int32_t n_members,
+                                        int64_t tiles_per_chunk /* >= 1 */);   /* a multiple of 256, monotone in tiles_per_chunk; -1 outside the caps */
+int mms_joint_sweep(const int64_t* query_id, const int64_t* product_id, const float* members /* [n_members][n] */, int32_t n_members, int64_t n,
+                    const int64_t* key_query, const int64_t* key_off, const int64_t* key_product, int64_t n_key_queries, int64_t n_key_products,
+                    const double* weights /* device [n_weights][n_members] */, int64_t n_weights,
+                    const double* filters /* device [n_filters][2] = (gap, tie) */, int64_t n_filters, int32_t k /* 1..5 */, int32_t allow_missing,
+                    const double* bin_value /* device [(k+1)<<k] or NULL */, int64_t n_key_queries_total /* divisor of value_out */,
+                    void* workspace, int64_t workspace_bytes, int64_t* hist_out /* [n_weights][n_filters][(k+1)<<k] or NULL; zeroed by the call */,
+                    double* value_out /* [n_weights][n_filters] or NULL; needs bin_value */, int32_t* status /* [4] as mms_ndcg_at_k */, void* stream);
 
 /* accumulated hipEvent time (ms) and launch count of the GEMM kernels since the last reset;
  * enable = 1 brackets every GEMM launch with events on its stream (bench / roofline only) */

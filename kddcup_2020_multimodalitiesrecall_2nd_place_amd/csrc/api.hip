@@ -1904,6 +1904,41 @@ int mms_filter_sweep(const int64_t* query_id, const int64_t* product_id, const f
     return 0;
 }
 
+int64_t mms_joint_sweep_workspace_bytes(int64_t n, int64_t n_key_queries, int64_t n_key_products, int32_t n_members, int64_t tiles_per_chunk) {
+    if (mms_ndcg_workspace_bytes(n, n_key_queries, n_key_products) < 0 || n_members < 1 || n_members > MMS_SWEEP_MAX_MEMBERS) return -1;
+    if (tiles_per_chunk < 1 || tiles_per_chunk > MMS_JOINT_MAX_ITEMS / 64) return -1;
+    return (int64_t)joint_sweep_workspace_bytes(n, n_key_queries, n_key_products, n_members, tiles_per_chunk);
+}
+
+int mms_joint_sweep(const int64_t* query_id, const int64_t* product_id, const float* members, int32_t n_members, int64_t n, const int64_t* key_query,
+                    const int64_t* key_off, const int64_t* key_product, int64_t n_key_queries, int64_t n_key_products, const double* weights,
+                    int64_t n_weights, const double* filters, int64_t n_filters, int32_t k, int32_t allow_missing, const double* bin_value,
+                    int64_t n_key_queries_total, void* workspace, int64_t workspace_bytes, int64_t* hist_out, double* value_out, int32_t* status,
+                    void* stream) {
+    // (the shared checks with a workspace of 0 bytes required: the sweep's own size is checked below)
+    const char* bad = ndcg_args(query_id, product_id, n, key_query, key_off, key_product, n_key_queries, n_key_products, workspace, INT64_MAX, status);
+    if (!bad && (n_members < 1 || n_members > MMS_SWEEP_MAX_MEMBERS)) bad = "n_members must be in [1, MMS_SWEEP_MAX_MEMBERS]";
+    if (!bad && (n_weights < 0 || n_weights > MMS_JOINT_MAX_ITEMS)) bad = "n_weights must be in [0, MMS_JOINT_MAX_ITEMS]";
+    if (!bad && (n_filters < 0 || n_filters > MMS_FILTER_MAX)) bad = "n_filters must be in [0, MMS_FILTER_MAX]";
+    if (!bad && n_weights * n_filters > MMS_JOINT_MAX_ITEMS) bad = "n_weights * n_filters must be at most MMS_JOINT_MAX_ITEMS";
+    if (!bad && (k < 1 || k > MMS_FILTER_MAX_K)) bad = "k must be in [1, MMS_FILTER_MAX_K]";
+    if (!bad && n > 0 && !members) bad = "null pointer";
+    if (!bad && ((n_weights > 0 && !weights) || (n_filters > 0 && !filters))) bad = "null pointer";
+    if (!bad && value_out && !bin_value) bad = "value_out needs bin_value";
+    if (!bad && value_out && n_key_queries_total < 1) bad = "value_out needs n_key_queries_total >= 1";
+    if (!bad && n_key_queries > 0 &&
+        joint_sweep_chunk_tiles(n, n_key_queries, n_key_products, n_members, n_weights, n_filters, k, hist_out != nullptr, workspace_bytes) < 1)
+        bad = "workspace smaller than mms_joint_sweep_workspace_bytes(n, n_key_queries, n_key_products, n_members, 1) (plus one tile's histograms without hist_out)";
+    if (bad) { g_err = std::string("mms_joint_sweep: ") + bad; return MMS_ERR_ARG; }
+    // (only enqueues: fills and kernels; no allocation, no synchronisation, nothing read back)
+    launch_joint_sweep(query_id, product_id, members, n_members, (int)n, key_query, key_off, key_product, (int)n_key_queries, (int)n_key_products, weights,
+                       n_weights, filters, n_filters, k, allow_missing != 0, bin_value, n_key_queries_total, workspace, workspace_bytes, hist_out, value_out,
+                       status, (hipStream_t)stream);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { g_err = std::string("mms_joint_sweep: ") + hipGetErrorString(e); return MMS_ERR_HIP; }
+    return 0;
+}
+
 int mms_create(const mms_config* cfg, mms_handle** out) {
     if (!cfg || !out) { g_err = "null argument"; return MMS_ERR_ARG; }
     *out = nullptr;

@@ -286,6 +286,7 @@ void launch_decode_feats_b64(const char* chars, const int64_t* char_off, const i
 // rank.hip: uniqueness filter + per-query top-5 of the merged scores (mms_rank_submission checks the arguments; n <= MMS_RANK_MAX_ROWS, workspace of
 // rank_workspace_bytes(n) bytes, 256-byte aligned).  Enqueues three fills and eight kernels on st; allocates nothing, waits for nothing.
 long long rank_workspace_bytes(long long n);
+int rank_table_slots(long long n);   // slots of its open-addressing tables (a power of two >= 1024, >= 2 n): the range of RankStats::pslot
 void launch_rank_submission(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int n, double gap,
                             double tie, void* workspace, int max_queries, int64_t* out_query, int64_t* out_products, int32_t* out_count,
                             int32_t* status, hipStream_t st);
@@ -326,3 +327,15 @@ void launch_filter_sweep(const int64_t* query_id, const int64_t* product_id, con
                          const int64_t* key_query, const int64_t* key_off, const int64_t* key_product, int Qa, int Tk, const double* filters,
                          long long n_filters, int k, int allow_missing, const double* bin_value, long long n_key_queries_total, void* workspace,
                          int64_t* hist_out, double* value_out, int32_t* code_out, int32_t* status, hipStream_t st);
+// joint_sweep.hip: nDCG@k histograms (and values) of the submission rows for every (weight vector, filter) pair: item v * n_filters + g is what
+// launch_filter_sweep yields for filter g on the merge of launch_ndcg_sweep for vector v (mms_joint_sweep checks the arguments; k in 1..5).  The weight
+// tiles (64 vectors) are swept in chunks of joint_sweep_chunk_tiles(...) tiles: what fits in workspace_bytes (0: not even one).  hist_out == nullptr: the
+// chunk's histograms live in the workspace (64 * n_filters * bins * 8 bytes per tile on top of joint_sweep_workspace_bytes) and only values are written.
+// Enqueues fills and fifteen kernels, then four kernels and at most one fill per chunk, on st; allocates nothing, waits for nothing.
+long long joint_sweep_workspace_bytes(long long n, long long n_key_queries, long long n_key_products, int n_members, long long tiles_per_chunk);
+long long joint_sweep_chunk_tiles(long long n, long long n_key_queries, long long n_key_products, int n_members, long long n_weights, long long n_filters,
+                                  int k, bool have_hist, long long workspace_bytes);
+void launch_joint_sweep(const int64_t* query_id, const int64_t* product_id, const float* members, int n_members, int n, const int64_t* key_query,
+                        const int64_t* key_off, const int64_t* key_product, int Qa, int Tk, const double* weights, long long n_weights,
+                        const double* filters, long long n_filters, int k, int allow_missing, const double* bin_value, long long n_key_queries_total,
+                        void* workspace, long long workspace_bytes, int64_t* hist_out, double* value_out, int32_t* status, hipStream_t st);

@@ -40,10 +40,19 @@ struct RankWs {              // device workspace carved by rank_layout(); [cap] 
     size_t ff_bytes, zero_bytes, total_bytes;
 };
 
-RankWs rank_layout(void* base, long long n) {
-    RankWs w{};
+}  // namespace
+
+int rank_table_slots(long long n) {
     int cap = 1024;
     while (cap < 2 * n) cap <<= 1;
+    return cap;
+}
+
+namespace {
+
+RankWs rank_layout(void* base, long long n) {
+    RankWs w{};
+    const int cap = rank_table_slots(n);
     w.cap = cap; w.mask = (unsigned)(cap - 1);
     Carver cv{(char*)base, 0};
     const size_t c = (size_t)cap, r = (size_t)(n > 0 ? n : 1), nb = (r + SCAN_ROWS - 1) / SCAN_ROWS;

@@ -5,7 +5,7 @@
 //   lists      block_scan / scan_top (exclusive scan over a workgroup, block sums -> prefixes), scatter_rows (counting-sort scatter by wavefront
 //              runs), ranks_before / wave_next (one round of the wave-wide arg-max selection)
 //   sweeps     TopK (register top-K list of k_sweep; k_filter_sweep writes the same steps out), sweep_task / sweep_zero / sweep_flush / sweep_grid (the (tile, slab) task walk and its
-//              [bins][64] LDS histogram)
+//              [bins][64] LDS histogram; sweep_flush_strided: the flush of joint_sweep.hip, whose tile's items lie n_filters apart)
 // Comparisons, integer work and data movement only: the floating-point arithmetic that defines a result stays in the .hip files, below their
 // own fp-contract pragma.  Each translation unit gets its own copy.
 #pragma once
@@ -229,6 +229,17 @@ __device__ __forceinline__ void sweep_flush(const int* counters, long long tile,
         const int c = counters[x];
         const long long item = tile * 64 + (x & 63);
         if (c != 0 && item < n_items) atomicAdd(&hist[(size_t)item * BINS + (x >> 6)], (u64)c);
+    }
+    __syncthreads();
+}
+// the same with the tile's lanes `stride` items apart: lane l of the tile adds to item item0 + l * stride (lanes >= n_lanes are padding)
+template <int BINS>
+__device__ __forceinline__ void sweep_flush_strided(const int* counters, long long item0, long long stride, long long n_lanes, u64* hist) {
+    __syncthreads();
+    for (int x = threadIdx.x; x < BINS * 64; x += 256) {
+        const int c = counters[x];
+        const long long l = x & 63;
+        if (c != 0 && l < n_lanes) atomicAdd(&hist[(size_t)(item0 + l * stride) * BINS + (x >> 6)], (u64)c);
     }
     __syncthreads();
 }

@@ -314,3 +314,43 @@ def fit_filter(query_id, product_id, score, rank_label, filters=None, k: int = 5
                          lambda to_np: ndcg.filter_sweep_host(to_np(query_id), to_np(product_id), to_np(score), filters, label_dict, k, allow_missing)[0],
                          where == "device" and len(label_dict), info)
     return (float(filters[index, 0]), float(filters[index, 1])), float(values[index]), index, values
+
+
+def fit_joint(query_id, product_id, members, rank_label, grid=None, filters=None, k: int = 5, allow_missing: bool = False, where: str = "device",
+              info: dict = None):
+    """The merge weights AND the uniqueness filter as ONE result of the valid set: nDCG@k of the SUBMISSION rows (``ndcg.submission_codes`` on the
+    merge ``ndcg.merge_members(members, w)``) for every pair of a row ``w`` of ``grid`` (default ``weight_grid(M, 20)``) and a row ``(gap, tie)`` of
+    ``filters`` (default ``filter_grid()``), and the winner -- the FIRST pair that attains the maximum in row-major (weight-major) order.  The filter's
+    decisions move with the weights, so this optimum can lie strictly above ``fit_weights`` followed by ``fit_filter``, which fits the weights on the
+    unfiltered ranking.  -> (weights tuple, (gap, tie), value, (iw, ig), values float64 numpy [W, G]).
+    ``where="device"``: ``ndcg.joint_sweep_device`` (``mms_joint_sweep``: one call for both grids); ONE synchronising read carries the status and the
+    values.  What the device does not do -- a (query, product) pair that occurs twice, a non-finite merged score in any row, a repeated key query, a
+    reserved id -- it detects: the values then come from ``ndcg.joint_sweep_host``, which ``where="host"`` runs directly; both give the same floats,
+    bit for bit.  A key query without rows raises ``KeyError`` unless ``allow_missing``.  ``info`` receives ``{"path", "flags"}``."""
+    import numpy as np
+
+    from . import ndcg
+    if where not in ("host", "device"):
+        raise ValueError("where must be 'host' or 'device', not %r" % (where,))
+    label_dict = rank_label.rank_label if isinstance(rank_label, ndcg.AnswerKey) else rank_label
+    M = len(members)
+    grid = weight_grid(M, 20) if grid is None else np.ascontiguousarray(grid, np.float64)
+    if grid.ndim != 2 or grid.shape[0] == 0:
+        raise ValueError("fit_joint: the grid must be [W >= 1, %d]" % M)
+    filters = filter_grid() if filters is None else np.ascontiguousarray(filters, np.float64)
+    if filters.ndim != 2 or filters.shape[1] != 2 or filters.shape[0] == 0:
+        raise ValueError("fit_joint: the filters must be [G >= 1, 2] rows of (gap, tie)")
+    W, G = grid.shape[0], filters.shape[0]
+
+    def device_call():
+        values, _, status = ndcg.joint_sweep_device(query_id, product_id, members, grid, filters, rank_label, k, allow_missing)
+        return values.reshape(-1), None, status
+
+    def host_call(to_np):
+        mem = np.stack([to_np(m) for m in members]) if isinstance(members, (list, tuple)) else to_np(members)
+        return ndcg.joint_sweep_host(to_np(query_id), to_np(product_id), mem, grid, filters, label_dict, k, allow_missing)[0].reshape(-1)
+
+    index, values = _fit(device_call, host_call, where == "device" and len(label_dict), info)
+    iw, ig = divmod(index, G)
+    return (tuple(float(x) for x in grid[iw]), (float(filters[ig, 0]), float(filters[ig, 1])), float(values[index]), (iw, ig),
+            values.reshape(W, G))

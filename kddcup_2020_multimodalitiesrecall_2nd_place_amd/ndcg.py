@@ -470,3 +470,87 @@ def filter_sweep_device(query_id, product_id, score, filters, rank_label, k: int
                             _ptr(hist), _ptr(values), _ptr(codes), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     _check_rc(l, rc, "mms_filter_sweep")
     return (values, hist, status, codes) if want_codes else (values, hist, status)
+
+
+# ---- joint sweep: nDCG@k of the SUBMISSION rows for every (weight vector, filter) pair (mms_joint_sweep, csrc/joint_sweep.hip) ----
+MAX_JOINT_ITEMS = 1 << 22                                                                  # MMS_JOINT_MAX_ITEMS
+JOINT_STATS_BYTES = 256 << 20             # joint_sweep_device's default chunk: the weight tiles whose product statistics fit in this
+
+
+def _member_array(members):
+    mem = np.stack([np.asarray(m).reshape(-1) for m in members]) if isinstance(members, (list, tuple)) and members else np.asarray(members)
+    return mem.astype(np.float32) if mem.dtype != np.float32 else mem
+
+
+def _joint_args(members, weights, n_filters, k):
+    _filter_k(k)
+    _sweep_args(members, weights, k)
+    if weights.shape[0] > MAX_JOINT_ITEMS or weights.shape[0] * n_filters > MAX_JOINT_ITEMS:
+        raise ValueError("at most %d (weight vector, filter) pairs per call" % MAX_JOINT_ITEMS)
+
+
+def joint_sweep_host(query_id, product_id, members, weights, filters, rank_label: dict, k: int = 5, allow_missing: bool = False):
+    """The host form of the joint sweep and the reference of the device form -- by definition the loop: per weight vector ``w`` of ``weights``
+    (float64 [W, M]) ``filter_sweep_host`` of ``filters`` (float64 [G, 2] rows ``(gap, tie)``) on ``merge_members(members, w)``.  It composes the two
+    existing contracts (the merge of the weight sweep feeds the filter sweep unchanged) and adds no arithmetic of its own.  ``members``: float32
+    [M, n], member-major.  -> (values float64 [W, G], hist int64 [W, G, (k + 1) << k]), numpy."""
+    mem = _member_array(members)
+    wts = np.asarray(weights, np.float64)
+    f = _filter_array(filters)
+    _joint_args(mem, wts, f.shape[0], k)
+    label_dict = rank_label.rank_label if isinstance(rank_label, AnswerKey) else rank_label
+    mem = mem.reshape(mem.shape[0], -1)
+    values = np.empty((wts.shape[0], f.shape[0]), np.float64)
+    hist = np.empty((wts.shape[0], f.shape[0], (k + 1) << k), np.int64)
+    for v in range(wts.shape[0]):
+        values[v], hist[v], _ = filter_sweep_host(query_id, product_id, merge_members(mem, wts[v]), f, label_dict, k, allow_missing)
+    return values, hist
+
+
+def joint_sweep_device(query_id, product_id, members, weights, filters, rank_label, k: int = 5, allow_missing: bool = False, want_hist: bool = False,
+                       chunk_tiles: int = None):
+    """``mms_joint_sweep``: the joint sweep on the GPU in one call.  ``members`` [M, n] fp32, ``weights`` [W, M] fp64 and ``filters`` [G, 2] fp64 are
+    used in place when they are contiguous device tensors of that dtype, host arrays are copied up once; ``rank_label``: the ``{query: [products]}``
+    dict or an ``AnswerKey``.  -> (values float64 [W, G], hist int64 [W, G, (k + 1) << k] or None without ``want_hist``, status int32 [4]), device
+    tensors, equal to ``joint_sweep_host`` -- integers entry for entry, values bit for bit -- while the flag word ``status[2]`` is zero (or
+    "missing" alone with ``allow_missing``).  The weight vectors are swept in chunks of ``chunk_tiles`` tiles of 64 (``None``: as many as keep the
+    per-vector product statistics within 256 MiB, one at least); the result does not depend on it.  Without ``want_hist`` the histograms of one
+    chunk live in the workspace and the full [W, G, bins] array (about 280 MB at the default grids) is never allocated.
+    Only enqueues on the current stream: nothing is read back, nothing waits."""
+    import torch
+
+    from . import lib as _lib
+    (q, p), dev = _rows_on_device((query_id, product_id), ((torch.int64,), (torch.int64,)), "joint_sweep_device")
+    to_t = lambda x, dt: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).to(device=dev, dtype=dt, non_blocking=True).contiguous()
+    if isinstance(members, (list, tuple)):
+        members = torch.stack([to_t(m, torch.float32).reshape(-1) for m in members]) if members else torch.zeros((0, 0))
+    mem, wts = to_t(members, torch.float32), to_t(weights, torch.float64)
+    flt = to_t(filters if torch.is_tensor(filters) else _filter_array(filters), torch.float64)
+    if flt.ndim != 2 or flt.shape[1] != 2 or flt.shape[0] > MAX_FILTERS:
+        raise ValueError("filters must be [G <= %d, 2] rows of (gap, tie), not %s" % (MAX_FILTERS, tuple(flt.shape)))
+    _joint_args(mem, wts, flt.shape[0], k)
+    n, M, W, G = q.shape[0], mem.shape[0], wts.shape[0], flt.shape[0]
+    if mem.shape[1] != n:
+        raise ValueError("joint_sweep_device: %d rows, member scores of %d" % (n, mem.shape[1]))
+    key = _key_on(rank_label, dev)
+    if key.n_queries == 0:
+        raise ValueError("joint_sweep_device: empty answer key")
+    if chunk_tiles is not None and chunk_tiles < 1:
+        raise ValueError("joint_sweep_device: chunk_tiles must be >= 1")
+    l = _lib.load()
+    bins = (k + 1) << k
+    tiles = max(1, (W + 63) // 64)
+    chunk = min(tiles, max(1, JOINT_STATS_BYTES // (16 * 64 * max(n, 1))) if chunk_tiles is None else int(chunk_tiles))
+    ws_bytes = l.mms_joint_sweep_workspace_bytes(n, key.n_queries, key.n_products, M, chunk)
+    if ws_bytes >= 0 and not want_hist:
+        ws_bytes += chunk * ((64 * G * bins * 8 + 255) & ~255)                 # the chunk's histograms
+    ws, ws_bytes = _workspace(ws_bytes, n, key, dev, "joint_sweep_device")
+    table = _bin_table(k, dev)
+    hist = torch.empty((W, G, bins), dtype=torch.int64, device=dev) if want_hist else None
+    values = torch.empty((W, G), dtype=torch.float64, device=dev)
+    status = torch.empty((4,), dtype=torch.int32, device=dev)
+    rc = l.mms_joint_sweep(_ptr(q), _ptr(p), _ptr(mem), M, n, _ptr(key.key_query), _ptr(key.key_off), _ptr(key.key_product), key.n_queries,
+                           key.n_products, _ptr(wts), W, _ptr(flt), G, k, int(bool(allow_missing)), table.data_ptr(), key.n_queries, ws.data_ptr(), ws_bytes,
+                           _ptr(hist), _ptr(values), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    _check_rc(l, rc, "mms_joint_sweep")
+    return values, hist, status

@@ -500,6 +500,25 @@ class EnsembleScorer:
             scores_out.update(query_id=qid, product_id=pid, score=score)
         return ensemble.fit_filter(qid, pid, score, rank_label, filters, k, info=info)
 
+    def fit_joint_tsv_native(self, tsv_path, vocab_path, label_table, rank_label, grid=None, filters=None, k: int = 5, labels: str = "answer",
+                             batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host", info: dict = None, scores_out: dict = None):
+        """A valid TSV file -> the merge weights AND the uniqueness filter ``(gap, tie)`` that TOGETHER maximise the nDCG@k of the SUBMISSION rows
+        against the answer key: ONE pass as ``fit_weights_tsv_native`` (the four member scores left on the device, the zk members' label feed as
+        ``labels`` says), then ``ensemble.fit_joint`` over ``grid`` x ``filters`` (defaults ``ensemble.weight_grid(4, 20)`` x
+        ``ensemble.filter_grid()``: 1 771 x 102 pairs) in one library call (``mms_joint_sweep``).
+        -> (weights tuple, (gap, tie), value, (iw, ig), values numpy [W, G]), the tuple of ``fit_joint``; pass the winner to ``set_weights`` and to
+        ``submission_tsv_native(gap=, tie=)``.  The scorer's own weights are NOT changed.  ``scores_out`` (a dict) receives ``query_id`` /
+        ``product_id`` (numpy) and ``members`` (device fp32 [4, n]).  The value is that of main.py's DOUBLE merge of the fp32 member scores; the
+        fused call ranks the fp32 merge, which can differ on a near tie."""
+        from . import ensemble
+        _check_eval_args("device", labels)
+        rank_label, relabel = _relabel(labels, rank_label, self.zk.device)
+        qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=True, relabel=relabel)
+        mem = torch.cat([m for _, m in out], 1) if out else torch.zeros((4, 0), dtype=torch.float32, device=self.zk.device)
+        if scores_out is not None:
+            scores_out.update(query_id=qid, product_id=pid, members=mem)
+        return ensemble.fit_joint(qid, pid, mem, rank_label, grid, filters, k, info=info)
+
     def score_tsv_native(self, tsv_path, vocab_path, label_table, batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host"):
         """``score_lines`` on a TSV file through libmmfeat, decode and scoring overlapped: a producer thread decodes span batch i+1
         three times (zk flavour, zk with the sen2forest rewrite, lxmert flavour; ctypes releases the GIL, each featurizer rotates
