@@ -174,11 +174,11 @@ typedef struct mms_ensemble_batch {
 /* ABI revision of the structs and entry points declared in this header.  It changes whenever a struct gains a field or an entry
  * point changes its signature (r1: 1; r2 added mms_config.fuse_layernorm, mms_zk_batch.label_ids, mms_lxmert_batch.label_ids / x_norm
  * without bumping it; r3: 3, then 4 with mms_config.fuse_attention; r4: 5 -- mms_dbg_gemm takes the engine per call,
- * the process-global mms_set_gemm_variant and the lab engines' hooks left the product library, fuse_layernorm became a mask; r5: 6 -- mms_dbg_qkv_attn and mms_side_lane_flops added; r7: 7 -- mms_decode_feats_b64 added; r8: 8 -- mms_rank_workspace_bytes and mms_rank_submission added; r9: 9 -- mms_ndcg_workspace_bytes, mms_key_relevance and mms_ndcg_at_k added; r10: 10 -- mms_ndcg_sweep_workspace_bytes and mms_ndcg_weight_sweep added; r11: 11 -- mms_filter_sweep_workspace_bytes and mms_filter_sweep added; r12: 12 -- mms_joint_sweep_workspace_bytes and mms_joint_sweep added).  A caller built against another revision would make the library read past its structs, so compare
+ * the process-global mms_set_gemm_variant and the lab engines' hooks left the product library, fuse_layernorm became a mask; r5: 6 -- mms_dbg_qkv_attn and mms_side_lane_flops added; r7: 7 -- mms_decode_feats_b64 added; r8: 8 -- mms_rank_workspace_bytes and mms_rank_submission added; r9: 9 -- mms_ndcg_workspace_bytes, mms_key_relevance and mms_ndcg_at_k added; r10: 10 -- mms_ndcg_sweep_workspace_bytes and mms_ndcg_weight_sweep added; r11: 11 -- mms_filter_sweep_workspace_bytes and mms_filter_sweep added; r12: 12 -- mms_joint_sweep_workspace_bytes and mms_joint_sweep added; r13: 13 -- mms_joint_sweep_codes, mms_resample_workspace_bytes and mms_resample_select added).  A caller built against another revision would make the library read past its structs, so compare
  * BEFORE the first mms_create:  if (mms_version() != MMS_ABI_VERSION) abort();   (lib.py's load() does) */
-#define MMS_ABI_VERSION 12
+#define MMS_ABI_VERSION 13
 int mms_version(void);
-const char* mms_global_error(void);              /* message of the last failing mms_create / mms_decode_feats_b64 / mms_rank_submission / mms_key_relevance / mms_ndcg_at_k / mms_ndcg_weight_sweep / mms_filter_sweep / mms_joint_sweep */
+const char* mms_global_error(void);              /* message of the last failing mms_create / mms_decode_feats_b64 / mms_rank_submission / mms_key_relevance / mms_ndcg_at_k / mms_ndcg_weight_sweep / mms_filter_sweep / mms_joint_sweep / mms_joint_sweep_codes / mms_resample_select */
 
 int mms_create(const mms_config* cfg, mms_handle** out);
 void mms_destroy(mms_handle* h);
@@ -459,6 +459,65 @@ int mms_joint_sweep(const int64_t* query_id, const int64_t* product_id, const fl
                     const double* bin_value /* device [(k+1)<<k] or NULL */, int64_t n_key_queries_total /* divisor of value_out */,
                     void* workspace, int64_t workspace_bytes, int64_t* hist_out /* [n_weights][n_filters][(k+1)<<k] or NULL; zeroed by the call */,
                     double* value_out /* [n_weights][n_filters] or NULL; needs bin_value */, int32_t* status /* [4] as mms_ndcg_at_k */, void* stream);
+
+/* mms_joint_sweep that KEEPS the per-query codes: the same call -- launch sequence, histograms, values, status and workspace sizes, bit for bit and
+ * whatever the chunk -- plus code_out, one byte per (filter g, key query i, weight vector v):
+ *       code_out[(g * n_key_queries + i) * Wp + v],   Wp = 64 * ceil(n_weights / 64)
+ *   ideal << 5 | mask   a graded query: the int32 code mask | ideal << 8 of mms_filter_sweep's code_out (k <= 5: mask < 32, ideal <= 5)
+ *   0xFF                a key query without table rows (code -1)
+ *   0xFE                a key query with rows but no output row (code -2)
+ * The 64 lanes of a wavefront own 64 consecutive vectors, so the store is one aligned 64-byte line per (filter, key query, tile).  The call fills
+ * the matrix with 0xFF first; bytes with v >= n_weights are unspecified and never read.  ndcg.joint_codes_host on the host.
+ * code_bytes must equal n_filters * n_key_queries * Wp (0 with code_out == NULL, which makes the call mms_joint_sweep): MMS_ERR_ARG otherwise, nothing
+ * launched.  The other arguments, errors and empty cases are mms_joint_sweep's. */
+int mms_joint_sweep_codes(const int64_t* query_id, const int64_t* product_id, const float* members /* [n_members][n] */, int32_t n_members, int64_t n,
+                          const int64_t* key_query, const int64_t* key_off, const int64_t* key_product, int64_t n_key_queries, int64_t n_key_products,
+                          const double* weights /* device [n_weights][n_members] */, int64_t n_weights,
+                          const double* filters /* device [n_filters][2] = (gap, tie) */, int64_t n_filters, int32_t k /* 1..5 */, int32_t allow_missing,
+                          const double* bin_value /* device [(k+1)<<k] or NULL */, int64_t n_key_queries_total /* divisor of value_out */,
+                          void* workspace, int64_t workspace_bytes, int64_t* hist_out /* [n_weights][n_filters][(k+1)<<k] or NULL; zeroed by the call */,
+                          double* value_out /* [n_weights][n_filters] or NULL; needs bin_value */,
+                          uint8_t* code_out /* [n_filters][n_key_queries][Wp] or NULL */, int64_t code_bytes, int32_t* status /* [4] as mms_ndcg_at_k */,
+                          void* stream);
+
+/* Resampling the joint fit: k-fold, repeated k-fold and bootstrap estimates of the HELD-OUT nDCG@k from the codes of ONE sweep.  The filter's product
+ * statistics are taken over all rows of the table whatever the key, so the code of key query i under item (v, g) does not depend on which other key
+ * queries are graded: a replicate is a row of small integer counts over the key queries, its value a count-weighted mean over the item's codes.
+ *   code        device, the matrix of mms_joint_sweep_codes for n_weights x n_filters items and n_key_queries key queries; code_bytes as there
+ *   count_fit / count_eval   device uint8 [n_replicates][n_key_queries]: how often key query i counts in the fit / in the evaluation of replicate r
+ *   byte_value  device fp64 [256]: the value of a key query per code byte (ndcg.byte_values(k): ndcg._code_value of the byte's code; 0.0 for 0xFF, 0xFE
+ *               and the bytes that cannot occur at this k).  PRECONDITION: finite and >= 0
+ *   probe_item  device int64 [n_probes] (optional): items v * n_filters + g whose values are reported per replicate whoever wins
+ *   ARITHMETIC CONTRACT, IEEE double, never a fused multiply-add:
+ *       fit[r][item] = (sum over i = 0 .. n_key_queries - 1 of double(count_fit[r][i]) * byte_value[code[item][i]]) / double(sum over i of count_fit[r][i])
+ *   the sum in key order from +0.0, every product, every sum and the division rounded on its own (a term with count 0 adds +0.0 to a sum that is never
+ *   negative: the same bits as leaving it out; the divisor is the integer sum, converted once).  With all counts 1 this is ndcg.ndcg_from_codes of the
+ *   item's codes term for term -- the sum evaluate_ndcg makes.  ndcg.resample_select_host on the host.
+ *   best[r]        the SMALLEST item v * n_filters + g that attains the maximum of fit[r][.]: the first-at-maximum rule of ensemble.fit_joint
+ *   fit_value[r]   that maximum;   eval_value[r]  the same sum with count_eval[r] on item best[r] (a zero count sum: NaN, from 0.0 / 0.0)
+ *   probe_fit[r][p] / probe_eval[r][p]   the two sums on item probe_item[p] (an item outside [0, n_weights * n_filters): NaN, nothing is read)
+ *   flags (status[2]): bit 5 (MMS_FLAG_EMPTY_FIT) is OR-ed in when count_fit of some replicate sums to zero: best[r] = -1, fit_value[r] and
+ *   eval_value[r] NaN for that replicate.  Nothing else of status is written, so the status block of the sweep can be passed on and one read carries
+ *   every flag; a caller without a sweep zeroes it.
+ *   workspace: device memory, 256-byte aligned, mms_resample_workspace_bytes(n_weights, n_filters, n_key_queries, n_replicates) bytes.
+ * The [n_replicates][items] value matrix is never stored: a lane owns an item and walks its codes in key order with the counts of 16 replicates in
+ * scalar registers, a workgroup reduces its items to one (value, item) per replicate, and a second kernel picks per replicate by the total order
+ * (value descending, item ascending) and walks the winner's and the probes' codes (csrc/resample.hip).  No floating-point atomics: equal inputs give
+ * bit-equal outputs.  No kernel waits on another workgroup.  ONLY ENQUEUES on `stream` (four kernels): no allocation, no synchronisation, no
+ * device -> host read.  Handle-free.
+ * Returns MMS_ERR_ARG (message in mms_global_error naming the function, nothing launched) for a count that is negative or over its cap (n_weights and
+ * n_weights * n_filters <= MMS_JOINT_MAX_ITEMS, n_filters <= MMS_FILTER_MAX, n_key_queries <= MMS_NDCG_MAX_KEY_QUERIES, n_replicates <=
+ * MMS_RESAMPLE_MAX_REPLICATES, n_probes <= MMS_RESAMPLE_MAX_PROBES), a code_bytes other than n_filters * n_key_queries * Wp, a NULL pointer whose
+ * count is non-zero (status: always), a workspace that is too small or not 256-byte aligned.  n_replicates == 0: nothing is written. */
+#define MMS_RESAMPLE_MAX_REPLICATES (1 << 16)
+#define MMS_RESAMPLE_MAX_PROBES 256
+#define MMS_FLAG_EMPTY_FIT 32
+int64_t mms_resample_workspace_bytes(int64_t n_weights, int64_t n_filters, int64_t n_key_queries, int64_t n_replicates);   /* a multiple of 256; -1 outside the caps */
+int mms_resample_select(const uint8_t* code, int64_t code_bytes, int64_t n_weights, int64_t n_filters, int64_t n_key_queries,
+                        const uint8_t* count_fit, const uint8_t* count_eval /* device [n_replicates][n_key_queries] */, int64_t n_replicates,
+                        const double* byte_value /* device [256] */, const int64_t* probe_item /* device [n_probes] or NULL */, int64_t n_probes,
+                        void* workspace, int64_t workspace_bytes, int64_t* best /* [n_replicates] */, double* fit_value, double* eval_value /* [n_replicates] */,
+                        double* probe_fit, double* probe_eval /* [n_replicates][n_probes] */, int32_t* status /* [4]; [2] |= flags */, void* stream);
 
 /* accumulated hipEvent time (ms) and launch count of the GEMM kernels since the last reset;
  * enable = 1 brackets every GEMM launch with events on its stream (bench / roofline only) */

@@ -1910,11 +1910,13 @@ int64_t mms_joint_sweep_workspace_bytes(int64_t n, int64_t n_key_queries, int64_
     return (int64_t)joint_sweep_workspace_bytes(n, n_key_queries, n_key_products, n_members, tiles_per_chunk);
 }
 
-int mms_joint_sweep(const int64_t* query_id, const int64_t* product_id, const float* members, int32_t n_members, int64_t n, const int64_t* key_query,
-                    const int64_t* key_off, const int64_t* key_product, int64_t n_key_queries, int64_t n_key_products, const double* weights,
-                    int64_t n_weights, const double* filters, int64_t n_filters, int32_t k, int32_t allow_missing, const double* bin_value,
-                    int64_t n_key_queries_total, void* workspace, int64_t workspace_bytes, int64_t* hist_out, double* value_out, int32_t* status,
-                    void* stream) {
+namespace {
+// mms_joint_sweep and mms_joint_sweep_codes (name: the one the messages carry)
+int joint_sweep_entry(const char* name, const int64_t* query_id, const int64_t* product_id, const float* members, int32_t n_members, int64_t n,
+                      const int64_t* key_query, const int64_t* key_off, const int64_t* key_product, int64_t n_key_queries, int64_t n_key_products,
+                      const double* weights, int64_t n_weights, const double* filters, int64_t n_filters, int32_t k, int32_t allow_missing,
+                      const double* bin_value, int64_t n_key_queries_total, void* workspace, int64_t workspace_bytes, int64_t* hist_out, double* value_out,
+                      uint8_t* code_out, int64_t code_bytes, int32_t* status, void* stream) {
     // (the shared checks with a workspace of 0 bytes required: the sweep's own size is checked below)
     const char* bad = ndcg_args(query_id, product_id, n, key_query, key_off, key_product, n_key_queries, n_key_products, workspace, INT64_MAX, status);
     if (!bad && (n_members < 1 || n_members > MMS_SWEEP_MAX_MEMBERS)) bad = "n_members must be in [1, MMS_SWEEP_MAX_MEMBERS]";
@@ -1929,13 +1931,77 @@ int mms_joint_sweep(const int64_t* query_id, const int64_t* product_id, const fl
     if (!bad && n_key_queries > 0 &&
         joint_sweep_chunk_tiles(n, n_key_queries, n_key_products, n_members, n_weights, n_filters, k, hist_out != nullptr, workspace_bytes) < 1)
         bad = "workspace smaller than mms_joint_sweep_workspace_bytes(n, n_key_queries, n_key_products, n_members, 1) (plus one tile's histograms without hist_out)";
-    if (bad) { g_err = std::string("mms_joint_sweep: ") + bad; return MMS_ERR_ARG; }
+    if (!bad && code_bytes != (code_out ? n_filters * n_key_queries * ((n_weights + 63) / 64 * 64) : 0))
+        bad = code_out ? "code_bytes must be n_filters * n_key_queries * Wp, Wp = n_weights rounded up to a multiple of 64" : "code_bytes without code_out";
+    if (bad) { g_err = std::string(name) + ": " + bad; return MMS_ERR_ARG; }
     // (only enqueues: fills and kernels; no allocation, no synchronisation, nothing read back)
     launch_joint_sweep(query_id, product_id, members, n_members, (int)n, key_query, key_off, key_product, (int)n_key_queries, (int)n_key_products, weights,
                        n_weights, filters, n_filters, k, allow_missing != 0, bin_value, n_key_queries_total, workspace, workspace_bytes, hist_out, value_out,
-                       status, (hipStream_t)stream);
+                       code_out, status, (hipStream_t)stream);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_err = std::string("mms_joint_sweep: ") + hipGetErrorString(e); return MMS_ERR_HIP; }
+    if (e != hipSuccess) { g_err = std::string(name) + ": " + hipGetErrorString(e); return MMS_ERR_HIP; }
+    return 0;
+}
+}  // namespace
+
+int mms_joint_sweep(const int64_t* query_id, const int64_t* product_id, const float* members, int32_t n_members, int64_t n, const int64_t* key_query,
+                    const int64_t* key_off, const int64_t* key_product, int64_t n_key_queries, int64_t n_key_products, const double* weights,
+                    int64_t n_weights, const double* filters, int64_t n_filters, int32_t k, int32_t allow_missing, const double* bin_value,
+                    int64_t n_key_queries_total, void* workspace, int64_t workspace_bytes, int64_t* hist_out, double* value_out, int32_t* status,
+                    void* stream) {
+    return joint_sweep_entry("mms_joint_sweep", query_id, product_id, members, n_members, n, key_query, key_off, key_product, n_key_queries, n_key_products,
+                             weights, n_weights, filters, n_filters, k, allow_missing, bin_value, n_key_queries_total, workspace, workspace_bytes, hist_out,
+                             value_out, nullptr, 0, status, stream);
+}
+
+int mms_joint_sweep_codes(const int64_t* query_id, const int64_t* product_id, const float* members, int32_t n_members, int64_t n, const int64_t* key_query,
+                          const int64_t* key_off, const int64_t* key_product, int64_t n_key_queries, int64_t n_key_products, const double* weights,
+                          int64_t n_weights, const double* filters, int64_t n_filters, int32_t k, int32_t allow_missing, const double* bin_value,
+                          int64_t n_key_queries_total, void* workspace, int64_t workspace_bytes, int64_t* hist_out, double* value_out, uint8_t* code_out,
+                          int64_t code_bytes, int32_t* status, void* stream) {
+    return joint_sweep_entry("mms_joint_sweep_codes", query_id, product_id, members, n_members, n, key_query, key_off, key_product, n_key_queries,
+                             n_key_products, weights, n_weights, filters, n_filters, k, allow_missing, bin_value, n_key_queries_total, workspace,
+                             workspace_bytes, hist_out, value_out, code_out, code_bytes, status, stream);
+}
+
+namespace {
+const char* resample_counts(int64_t n_weights, int64_t n_filters, int64_t n_key_queries, int64_t n_replicates) {
+    if (n_weights < 0 || n_weights > MMS_JOINT_MAX_ITEMS) return "n_weights must be in [0, MMS_JOINT_MAX_ITEMS]";
+    if (n_filters < 0 || n_filters > MMS_FILTER_MAX) return "n_filters must be in [0, MMS_FILTER_MAX]";
+    if (n_weights * n_filters > MMS_JOINT_MAX_ITEMS) return "n_weights * n_filters must be at most MMS_JOINT_MAX_ITEMS";
+    if (n_key_queries < 0 || n_key_queries > MMS_NDCG_MAX_KEY_QUERIES) return "n_key_queries must be in [0, MMS_NDCG_MAX_KEY_QUERIES]";
+    if (n_replicates < 0 || n_replicates > MMS_RESAMPLE_MAX_REPLICATES) return "n_replicates must be in [0, MMS_RESAMPLE_MAX_REPLICATES]";
+    return nullptr;
+}
+}  // namespace
+
+int64_t mms_resample_workspace_bytes(int64_t n_weights, int64_t n_filters, int64_t n_key_queries, int64_t n_replicates) {
+    if (resample_counts(n_weights, n_filters, n_key_queries, n_replicates)) return -1;
+    return (int64_t)resample_workspace_bytes(n_weights, n_filters, n_key_queries, n_replicates);
+}
+
+int mms_resample_select(const uint8_t* code, int64_t code_bytes, int64_t n_weights, int64_t n_filters, int64_t n_key_queries, const uint8_t* count_fit,
+                        const uint8_t* count_eval, int64_t n_replicates, const double* byte_value, const int64_t* probe_item, int64_t n_probes,
+                        void* workspace, int64_t workspace_bytes, int64_t* best, double* fit_value, double* eval_value, double* probe_fit,
+                        double* probe_eval, int32_t* status, void* stream) {
+    const char* bad = resample_counts(n_weights, n_filters, n_key_queries, n_replicates);
+    if (!bad && (n_probes < 0 || n_probes > MMS_RESAMPLE_MAX_PROBES)) bad = "n_probes must be in [0, MMS_RESAMPLE_MAX_PROBES]";
+    if (!bad && !status) bad = "null status";
+    if (!bad && code_bytes != n_filters * n_key_queries * ((n_weights + 63) / 64 * 64))
+        bad = "code_bytes must be n_filters * n_key_queries * Wp, Wp = n_weights rounded up to a multiple of 64";
+    if (!bad && code_bytes > 0 && !code) bad = "null pointer";
+    if (!bad && n_replicates > 0 && (!byte_value || !best || !fit_value || !eval_value || !workspace)) bad = "null pointer";
+    if (!bad && n_replicates > 0 && n_key_queries > 0 && (!count_fit || !count_eval)) bad = "null pointer";
+    if (!bad && n_probes > 0 && (!probe_item || (n_replicates > 0 && (!probe_fit || !probe_eval)))) bad = "null pointer";
+    if (!bad && n_replicates > 0 && (reinterpret_cast<uintptr_t>(workspace) & 255)) bad = "workspace must be 256-byte aligned";
+    if (!bad && n_replicates > 0 && workspace_bytes < (int64_t)resample_workspace_bytes(n_weights, n_filters, n_key_queries, n_replicates))
+        bad = "workspace smaller than mms_resample_workspace_bytes(n_weights, n_filters, n_key_queries, n_replicates)";
+    if (bad) { g_err = std::string("mms_resample_select: ") + bad; return MMS_ERR_ARG; }
+    // (only enqueues: four kernels; no allocation, no synchronisation, nothing read back)
+    launch_resample_select(code, n_weights, n_filters, (int)n_key_queries, count_fit, count_eval, (int)n_replicates, byte_value, probe_item, (int)n_probes,
+                           workspace, best, fit_value, eval_value, probe_fit, probe_eval, status, (hipStream_t)stream);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { g_err = std::string("mms_resample_select: ") + hipGetErrorString(e); return MMS_ERR_HIP; }
     return 0;
 }
 

@@ -252,7 +252,8 @@ __device__ __forceinline__ BestD load_stats(const BestD* st, int prod) { return 
 template <int K, int MP>
 __global__ __launch_bounds__(256) void k_joint_sweep(const double* __restrict__ weights, long long W, int M, const double* __restrict__ filters, int G, long long tile0,
                                                      int Qa, int slabs, long long tasks, NdcgLists L, const JointRec<MP>* __restrict__ rec,
-                                                     const char* __restrict__ tiles, size_t tile_stride, size_t umask_off, u64* hist) {
+                                                     const char* __restrict__ tiles, size_t tile_stride, size_t umask_off, u64* hist,
+                                                     unsigned char* __restrict__ code_out, long long Wp) {
     constexpr int BINS = (K + 1) << K;
     __shared__ int counters[BINS * 64];                                      // [bin][lane of the tile]
     const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);    // (scalar: the query walk is wave-uniform)
@@ -266,6 +267,9 @@ __global__ __launch_bounds__(256) void k_joint_sweep(const double* __restrict__ 
         const double gap = filters[2 * g], tie = filters[2 * g + 1];
         const BestD* st = (const BestD*)(tiles + (size_t)tl * tile_stride) + lane;
         const unsigned char* um = (const unsigned char*)(tiles + (size_t)tl * tile_stride + umask_off) + lane;
+        // the byte codes of (filter g, key query i) for the tile's 64 vectors: one aligned 64-byte line (v < Wp, a multiple of 64: lanes past W write
+        // bytes that are never read); nullptr: no codes are kept (a wave-uniform branch)
+        unsigned char* cd = code_out ? code_out + (size_t)g * Qa * Wp + v : nullptr;
         sweep_zero<BINS>(counters);
         for (int i = task.q0 + wv; i < task.q1; i += 4) {                     // (i, cnt, off: the same in every lane of the wavefront)
             const int cnt = L.cnt[i];
@@ -306,12 +310,14 @@ __global__ __launch_bounds__(256) void k_joint_sweep(const double* __restrict__ 
             if (ns < 5) mask = um[(size_t)i * 64];                           // 1..4 survivors: the best rows overall
             const unsigned ideal = (unsigned)min(max(L.distinct[i], 0), K);
             if (live && ns > 0) atomicAdd(&counters[((ideal << K) | mask) * 64 + lane], 1);
+            if (cd) cd[(size_t)i * Wp] = ns > 0 ? (unsigned char)((ideal << 5) | mask) : (unsigned char)0xFE;      // 0xFE: rows but no output row
         }
         sweep_flush_strided<BINS>(counters, ((long long)tl * 64) * G + g, G, W - (tile0 + tl) * 64, hist);
     }
 }
 
-struct JointCall { const float* members; int M, n; const double* weights; long long W; const double* filters; int G, k, Qa; NdcgLists L; int* status; hipStream_t st; };
+struct JointCall { const float* members; int M, n; const double* weights; long long W; const double* filters; int G, k, Qa; NdcgLists L; int* status; hipStream_t st;
+                   unsigned char* code_out; };
 
 template <int MP>
 void launch_joint_once(const JointCall& c, const JointWs& j, const RankStats& S) {
@@ -336,7 +342,8 @@ void launch_joint_chunk(const JointCall& c, const JointWs& j, long long tile0, i
                        (const JointRec<MP>*)j.qrec, (unsigned char*)(j.tiles + j.umask_off), j.tile_bytes);
     const SweepGrid sg = sweep_grid((long long)tiles * c.G * 64, c.Qa);      // a unit per (tile, filter)
     hipLaunchKernelGGL((k_joint_sweep<K, MP>), dim3(sg.grid), block, 0, c.st, c.weights, c.W, c.M, c.filters, c.G, tile0, c.Qa, sg.slabs, sg.tasks, c.L,
-                       (const JointRec<MP>*)j.qrec, (const char*)j.tiles, j.tile_bytes, j.umask_off, hist);
+                       (const JointRec<MP>*)j.qrec, (const char*)j.tiles, j.tile_bytes, j.umask_off, hist, c.code_out,
+                       (c.W + 63) / 64 * 64);
 }
 
 template <int MP>
@@ -368,7 +375,9 @@ long long joint_sweep_chunk_tiles(long long n, long long Qa, long long Tk, int M
 void launch_joint_sweep(const int64_t* query_id, const int64_t* product_id, const float* members, int M, int n, const int64_t* key_query,
                         const int64_t* key_off, const int64_t* key_product, int Qa, int Tk, const double* weights, long long W, const double* filters,
                         long long G, int k, int allow_missing, const double* bin_value, long long n_key_queries_total, void* workspace,
-                        long long workspace_bytes, int64_t* hist_out, double* value_out, int32_t* status, hipStream_t st) {
+                        long long workspace_bytes, int64_t* hist_out, double* value_out, uint8_t* code_out, int32_t* status, hipStream_t st) {
+    // every byte 0xFF, "no rows": k_joint_sweep skips the key queries without rows (and nothing is swept without rows or without a key)
+    if (code_out && Qa > 0 && W > 0 && G > 0) (void)hipMemsetAsync(code_out, 0xFF, (size_t)G * (size_t)Qa * (size_t)((W + 63) / 64 * 64), st);
     const int bins = (k + 1) << k;
     const long long items = W * G;
     if (hist_out && items > 0) (void)hipMemsetAsync(hist_out, 0, (size_t)items * bins * 8, st);
@@ -380,7 +389,7 @@ void launch_joint_sweep(const int64_t* query_id, const int64_t* product_id, cons
             const JointWs j = joint_layout(workspace, n, Qa, Tk, M);
             const RankStats S = launch_rank_stats(query_id, product_id, members, nullptr, n, j.rank, j.rstatus, st);
             (void)hipMemsetAsync(j.pfill, 0, (size_t)j.cap * 4, st);
-            const JointCall c{members, M, n, weights, W, filters, (int)G, k, Qa, L, status, st};
+            const JointCall c{members, M, n, weights, W, filters, (int)G, k, Qa, L, status, st, code_out};
             const bool mp4 = joint_mp(M) == 4;
             if (mp4) launch_joint_once<4>(c, j, S);
             else launch_joint_once<8>(c, j, S);

@@ -331,6 +331,7 @@ void launch_filter_sweep(const int64_t* query_id, const int64_t* product_id, con
 // launch_filter_sweep yields for filter g on the merge of launch_ndcg_sweep for vector v (mms_joint_sweep checks the arguments; k in 1..5).  The weight
 // tiles (64 vectors) are swept in chunks of joint_sweep_chunk_tiles(...) tiles: what fits in workspace_bytes (0: not even one).  hist_out == nullptr: the
 // chunk's histograms live in the workspace (64 * n_filters * bins * 8 bytes per tile on top of joint_sweep_workspace_bytes) and only values are written.
+// code_out (optional): the byte code of (filter g, key query i, vector v) at (g * Qa + i) * Wp + v, Wp = n_weights rounded up to a multiple of 64 (mmscore.h).
 // Enqueues fills and fifteen kernels, then four kernels and at most one fill per chunk, on st; allocates nothing, waits for nothing.
 long long joint_sweep_workspace_bytes(long long n, long long n_key_queries, long long n_key_products, int n_members, long long tiles_per_chunk);
 long long joint_sweep_chunk_tiles(long long n, long long n_key_queries, long long n_key_products, int n_members, long long n_weights, long long n_filters,
@@ -338,4 +339,11 @@ long long joint_sweep_chunk_tiles(long long n, long long n_key_queries, long lon
 void launch_joint_sweep(const int64_t* query_id, const int64_t* product_id, const float* members, int n_members, int n, const int64_t* key_query,
                         const int64_t* key_off, const int64_t* key_product, int Qa, int Tk, const double* weights, long long n_weights,
                         const double* filters, long long n_filters, int k, int allow_missing, const double* bin_value, long long n_key_queries_total,
-                        void* workspace, long long workspace_bytes, int64_t* hist_out, double* value_out, int32_t* status, hipStream_t st);
+                        void* workspace, long long workspace_bytes, int64_t* hist_out, double* value_out, uint8_t* code_out, int32_t* status,
+                        hipStream_t st);
+// resample.hip: per replicate (a row of counts over the key queries) the first item at the maximum of the count-weighted mean of the byte codes' values
+// (mms_resample_select checks the arguments).  Enqueues four kernels on st; allocates nothing, waits for nothing.
+long long resample_workspace_bytes(long long n_weights, long long n_filters, long long n_key_queries, long long n_replicates);
+void launch_resample_select(const uint8_t* code, long long n_weights, long long n_filters, int Qa, const uint8_t* count_fit, const uint8_t* count_eval,
+                            int n_replicates, const double* byte_value, const int64_t* probe_item, int n_probes, void* workspace, int64_t* best,
+                            double* fit_value, double* eval_value, double* probe_fit, double* probe_eval, int32_t* status, hipStream_t st);

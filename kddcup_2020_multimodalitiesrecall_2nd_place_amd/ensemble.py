@@ -354,3 +354,131 @@ def fit_joint(query_id, product_id, members, rank_label, grid=None, filters=None
     iw, ig = divmod(index, G)
     return (tuple(float(x) for x in grid[iw]), (float(filters[ig, 0]), float(filters[ig, 1])), float(values[index]), (iw, ig),
             values.reshape(W, G))
+
+
+# ---- resampling the joint fit: held-out nDCG@k of the (weights, gap, tie) that fit_joint selects ----
+RESAMPLE_CODE_BUDGET = 4 << 30            # fit_joint_resampled's cap on the code matrix (G * Qa * Wp bytes): a cap, not a tuned number
+
+
+def kfold_counts(n_key_queries: int, folds: int = 5, repeats: int = 1, seed: int = 0):
+    """The replicates of a (repeated) k-fold split of the key queries: (count_fit, count_eval), uint8 [folds * repeats, n_key_queries].  Repeat ``t``
+    assigns key query i to fold ``default_rng(seed + t).permutation(n_key_queries)[i] % folds``; replicate ``t * folds + f`` fits on the queries
+    outside fold f (count 1) and evaluates on those inside, so every key query is held out exactly once per repeat."""
+    import numpy as np
+    if folds < 2 or repeats < 1:
+        raise ValueError("kfold_counts: folds must be >= 2 and repeats >= 1")
+    if folds > n_key_queries:
+        raise ValueError("kfold_counts: %d folds of %d key queries" % (folds, n_key_queries))
+    ev = np.zeros((repeats, folds, n_key_queries), np.uint8)
+    for t in range(repeats):
+        fold = np.random.default_rng(seed + t).permutation(n_key_queries) % folds
+        ev[t, fold, np.arange(n_key_queries)] = 1
+    ev = ev.reshape(repeats * folds, n_key_queries)
+    return (1 - ev).astype(np.uint8), ev
+
+
+def bootstrap_counts(n_key_queries: int, replicates: int = 200, seed: int = 0):
+    """Bootstrap replicates of the key queries: (count_fit, count_eval), uint8 [replicates, n_key_queries].  A fit row holds the multinomial counts of
+    n_key_queries draws with replacement (``default_rng(seed).multinomial``); the eval row is its out-of-bag indicator (1 where the count is 0)."""
+    import numpy as np
+    if n_key_queries < 1 or replicates < 1:
+        raise ValueError("bootstrap_counts: n_key_queries and replicates must be >= 1")
+    fit = np.random.default_rng(seed).multinomial(n_key_queries, np.full(n_key_queries, 1.0 / n_key_queries), size=replicates)
+    if fit.max() > 255:
+        raise ValueError("bootstrap_counts: a key query was drawn %d times, the counts are bytes" % int(fit.max()))
+    return fit.astype(np.uint8), (fit == 0).astype(np.uint8)
+
+
+def fit_joint_resampled(query_id, product_id, members, rank_label, grid=None, filters=None, k: int = 5, allow_missing: bool = False,
+                        scheme: str = "kfold", folds: int = 5, repeats: int = 4, replicates: int = 200, seed: int = 0, counts=None, probes=(),
+                        where: str = "device", info: dict = None, code_budget: int = RESAMPLE_CODE_BUDGET):
+    """``fit_joint`` AND how far its winner can be trusted: the maximum of W x G noisy estimates is biased upward, so the fit is repeated on
+    resampled answer keys and graded on the key queries each replicate left out -- from the per-query codes of ONE sweep
+    (``ndcg.joint_codes_device`` / ``mms_joint_sweep_codes``), because the filter's product statistics are taken over all rows whatever the key.
+    Replicates: ``scheme="kfold"`` -> ``kfold_counts(Qa, folds, repeats, seed)``, ``"bootstrap"`` -> ``bootstrap_counts(Qa, replicates, seed)``, or
+    ``counts=(count_fit, count_eval)`` uint8 [R, Qa] of the caller.  Per replicate the FIRST item at the maximum of the count-weighted mean of the
+    per-query values (``ndcg.resample_select_host``'s arithmetic) and that item's mean over the eval counts.  ``probes``: further ``(iw, ig)`` pairs
+    whose fit / eval values are reported per replicate -- the reference's constants, say; probe 0 is always the whole-key winner.
+    -> dict: ``whole`` (the tuple of ``fit_joint``, from the same sweep's values and bit-equal to it), ``winners`` int64 [R, 2] ((iw, ig); -1 for an
+    empty fit row), ``fit_values`` / ``eval_values`` [R], ``probe_fit`` / ``probe_eval`` [R, 1 + len(probes)], ``probes`` (the (iw, ig) list),
+    ``count_fit`` / ``count_eval``, and the summaries ``heldout`` (nan-mean of eval_values), ``optimism`` (nan-mean of fit - eval) and ``agreement``
+    (share of replicates that select the whole-key winner).
+    ``where="device"``: the sweep and ``mms_resample_select`` are enqueued back to back and ONE synchronising read carries status, values and the
+    resampled results.  Any flag ``fit_joint`` falls back on sends this call to the host forms too (``ndcg.joint_sweep_host``,
+    ``ndcg.joint_codes_host``, ``ndcg.resample_select_host``), which ``where="host"`` runs directly; ``info`` receives ``{"path", "flags"}``.
+    The code matrix takes G * Qa * 64 * ceil(W / 64) bytes (90 MB at the default grids on the valid set); over ``code_budget`` bytes (default
+    4 GiB) the call raises ``ValueError``: fit a coarser grid."""
+    import numpy as np
+
+    from . import ndcg
+    if where not in ("host", "device"):
+        raise ValueError("where must be 'host' or 'device', not %r" % (where,))
+    label_dict = rank_label.rank_label if isinstance(rank_label, ndcg.AnswerKey) else rank_label
+    M, Qa = len(members), len(label_dict)
+    grid = weight_grid(M, 20) if grid is None else np.ascontiguousarray(grid, np.float64)
+    if grid.ndim != 2 or grid.shape[0] == 0:
+        raise ValueError("fit_joint_resampled: the grid must be [W >= 1, %d]" % M)
+    filters = filter_grid() if filters is None else np.ascontiguousarray(filters, np.float64)
+    if filters.ndim != 2 or filters.shape[1] != 2 or filters.shape[0] == 0:
+        raise ValueError("fit_joint_resampled: the filters must be [G >= 1, 2] rows of (gap, tie)")
+    W, G = grid.shape[0], filters.shape[0]
+    code_bytes = G * Qa * ((W + 63) // 64 * 64)
+    if code_bytes > code_budget:
+        raise ValueError("fit_joint_resampled: the code matrix of %d x %d grid points and %d key queries takes %d bytes, over the budget of %d: "
+                         "fit a coarser grid (fewer weight steps or filters) or raise code_budget" % (W, G, Qa, code_bytes, code_budget))
+    if counts is not None:
+        count_fit, count_eval = (np.ascontiguousarray(c) for c in counts)
+    elif scheme == "kfold":
+        count_fit, count_eval = kfold_counts(Qa, folds, repeats, seed)
+    elif scheme == "bootstrap":
+        count_fit, count_eval = bootstrap_counts(Qa, replicates, seed)
+    else:
+        raise ValueError("scheme must be 'kfold' or 'bootstrap', not %r" % (scheme,))
+    count_fit, count_eval = ndcg._count_arrays(count_fit, count_eval, Qa)
+    R = count_fit.shape[0]
+    probes = [(int(a), int(b)) for a, b in probes]
+    if any(not (0 <= a < W and 0 <= b < G) for a, b in probes) or 1 + len(probes) > ndcg.MAX_PROBES:
+        raise ValueError("fit_joint_resampled: probes are at most %d (iw, ig) pairs inside the %d x %d grids" % (ndcg.MAX_PROBES - 1, W, G))
+    user_items = np.array([a * G + b for a, b in probes], np.int64)
+    P = 1 + len(probes)
+
+    values, res, flags = None, None, 0
+    if where == "device" and Qa:
+        import torch
+        dvalues, _, status, codes = ndcg.joint_codes_device(query_id, product_id, members, grid, filters, rank_label, k, allow_missing)
+        flat = dvalues.reshape(-1)
+        # the whole-key winner, the first item at the maximum, stays on the device as probe 0 (index plumbing on [W * G]; the read below checks it)
+        first = torch.where(flat == flat.max(), torch.arange(W * G, device=flat.device), W * G).min().reshape(1)
+        items = torch.cat([first, torch.from_numpy(user_items).to(flat.device)])
+        best, fv, ev, pf, pe, _ = ndcg.resample_select_device(codes, W, count_fit, count_eval, k, items, status)
+        host = torch.cat([status.to(torch.float64), first.to(torch.float64), flat, best.to(torch.float64), fv, ev, pf.reshape(-1), pe.reshape(-1)]).cpu().numpy()   # the one synchronising read
+        flags = int(host[2])
+        if flags & ~(ndcg.FLAG_MISSING_QUERY | ndcg.FLAG_EMPTY_FIT) == 0:
+            if flags & ndcg.FLAG_MISSING_QUERY:                                  # only without allow_missing
+                raise KeyError("%d key queries have no rows" % int(host[3]))
+            o = 5 + W * G
+            values = host[5:o].copy()
+            res = (host[o:o + R].astype(np.int64), host[o + R:o + 2 * R].copy(), host[o + 2 * R:o + 3 * R].copy(),
+                   host[o + 3 * R:o + 3 * R + R * P].reshape(R, P).copy(), host[o + 3 * R + R * P:].reshape(R, P).copy())
+            if int(host[4]) != int(np.argmax(values)):
+                raise RuntimeError("fit_joint_resampled: probe 0 is item %d, the whole-key winner item %d" % (int(host[4]), int(np.argmax(values))))
+    if info is not None:
+        info.update(path="device" if values is not None else "host", flags=flags)
+    if values is None:
+        to_np = lambda x: x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+        mem = np.stack([to_np(m) for m in members]) if isinstance(members, (list, tuple)) else to_np(members)
+        qh, ph = to_np(query_id), to_np(product_id)
+        values = ndcg.joint_sweep_host(qh, ph, mem, grid, filters, label_dict, k, allow_missing)[0].reshape(-1)
+        codes = ndcg.joint_codes_host(qh, ph, mem, grid, filters, label_dict, k, allow_missing)
+        res = ndcg.resample_select_host(codes, count_fit, count_eval, k, np.r_[np.int64(np.argmax(values)), user_items])
+    index = int(np.argmax(values))                                               # the first item that attains the maximum
+    iw, ig = divmod(index, G)
+    whole = (tuple(float(x) for x in grid[iw]), (float(filters[ig, 0]), float(filters[ig, 1])), float(values[index]), (iw, ig), values.reshape(W, G))
+    best, fit_values, eval_values, probe_fit, probe_eval = res
+    winners = np.where(best[:, None] >= 0, np.stack([best // G, best % G], 1), -1)
+    gap = fit_values - eval_values
+    heldout = float(np.mean(eval_values[~np.isnan(eval_values)])) if not np.isnan(eval_values).all() else float("nan")      # the nan-means
+    optimism = float(np.mean(gap[~np.isnan(gap)])) if not np.isnan(gap).all() else float("nan")
+    return dict(whole=whole, winners=winners, fit_values=fit_values, eval_values=eval_values, probe_fit=probe_fit, probe_eval=probe_eval,
+                probes=[(iw, ig)] + probes, count_fit=count_fit, count_eval=count_eval, heldout=heldout, optimism=optimism,
+                agreement=float(np.mean(best == index)) if R else float("nan"))

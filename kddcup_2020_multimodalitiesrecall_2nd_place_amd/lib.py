@@ -65,7 +65,7 @@ class RowsSpec(C.Structure):
                ("hm_col0", C.c_int32), ("hm_blocks", C.c_int32)]
 
 
-ABI_VERSION = 12    # include/mmscore.h MMS_ABI_VERSION
+ABI_VERSION = 13    # include/mmscore.h MMS_ABI_VERSION
 
 # enum Engine of csrc/regimes.h (mms_dbg_gemm / mms_dbg_gemm_bench name ONE GEMM engine per call; tests/test_abi.py holds the two lists together)
 ENGINES = {"ENG_AUTO": 0, "ENG_TILE_128": 1, "ENG_TILE_DMA": 3, "ENG_TILE": 4, "ENG_SKINNY": 5, "ENG_TILE_256": 16, "ENG_PP": 20, "ENG_PP_PERSIST": 26,
@@ -77,7 +77,8 @@ EXPORTS = ("mms_version", "mms_global_error", "mms_create", "mms_destroy", "mms_
            "mms_dbg_gemm_bench", "mms_dbg_counter", "mms_fused_timing", "mms_side_lane_flops", "mms_decode_feats_b64",
            "mms_dbg_attention_ex", "mms_dbg_pack_plan", "mms_dbg_dedup", "mms_dbg_layernorm_ex", "mms_dbg_gemm_ex", "mms_dbg_convert", "mms_dbg_gemm_rows", "mms_dbg_splitk_reduce", "mms_dbg_gemm_f8_rows", "mms_dbg_proj_ln_splitk_rows", "mms_dbg_layernorm_rows", "mms_rank_workspace_bytes", "mms_rank_submission",
            "mms_ndcg_workspace_bytes", "mms_key_relevance", "mms_ndcg_at_k", "mms_ndcg_sweep_workspace_bytes", "mms_ndcg_weight_sweep",
-           "mms_filter_sweep_workspace_bytes", "mms_filter_sweep", "mms_joint_sweep_workspace_bytes", "mms_joint_sweep")
+           "mms_filter_sweep_workspace_bytes", "mms_filter_sweep", "mms_joint_sweep_workspace_bytes", "mms_joint_sweep",
+           "mms_joint_sweep_codes", "mms_resample_workspace_bytes", "mms_resample_select")
 LAB_EXPORTS = ("mms_dbg_gemm_mx", "mms_lab_ln_trace")      # libmmscore_lab.so only
 
 _lib = None
@@ -129,6 +130,10 @@ def load(path=None):
     lib.mms_joint_sweep_workspace_bytes.argtypes = [i64, i64, i64, i32, i64]
     lib.mms_joint_sweep_workspace_bytes.restype = i64
     lib.mms_joint_sweep.argtypes = [vp, vp, vp, i32, i64, vp, vp, vp, i64, i64, vp, i64, vp, i64, i32, i32, vp, i64, vp, i64, vp, vp, vp, vp]
+    lib.mms_joint_sweep_codes.argtypes = [vp, vp, vp, i32, i64, vp, vp, vp, i64, i64, vp, i64, vp, i64, i32, i32, vp, i64, vp, i64, vp, vp, vp, i64, vp, vp]
+    lib.mms_resample_workspace_bytes.argtypes = [i64, i64, i64, i64]
+    lib.mms_resample_workspace_bytes.restype = i64
+    lib.mms_resample_select.argtypes = [vp, i64, i64, i64, i64, vp, vp, i64, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp]
     lib.mms_dbg_gemm_f8.argtypes = [vp, i64, i64, vp, i64, vp, i32, i32, vp, vp]
     lib.mms_dbg_gemm_f8_rows.argtypes = [vp, i64, i64, vp, i64, vp, i32, i32, vp, C.POINTER(RowsSpec), vp]
     if hasattr(lib, "mms_dbg_gemm_mx"):      # lab build

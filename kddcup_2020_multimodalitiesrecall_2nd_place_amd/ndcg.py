@@ -517,6 +517,11 @@ def joint_sweep_device(query_id, product_id, members, weights, filters, rank_lab
     per-vector product statistics within 256 MiB, one at least); the result does not depend on it.  Without ``want_hist`` the histograms of one
     chunk live in the workspace and the full [W, G, bins] array (about 280 MB at the default grids) is never allocated.
     Only enqueues on the current stream: nothing is read back, nothing waits."""
+    return _joint_sweep_call(query_id, product_id, members, weights, filters, rank_label, k, allow_missing, want_hist, chunk_tiles, False)
+
+
+def _joint_sweep_call(query_id, product_id, members, weights, filters, rank_label, k, allow_missing, want_hist, chunk_tiles, want_codes):
+    """``joint_sweep_device`` (``mms_joint_sweep``) or, with ``want_codes``, ``joint_codes_device`` (``mms_joint_sweep_codes``: the codes come fourth)."""
     import torch
 
     from . import lib as _lib
@@ -549,8 +554,183 @@ def joint_sweep_device(query_id, product_id, members, weights, filters, rank_lab
     hist = torch.empty((W, G, bins), dtype=torch.int64, device=dev) if want_hist else None
     values = torch.empty((W, G), dtype=torch.float64, device=dev)
     status = torch.empty((4,), dtype=torch.int32, device=dev)
-    rc = l.mms_joint_sweep(_ptr(q), _ptr(p), _ptr(mem), M, n, _ptr(key.key_query), _ptr(key.key_off), _ptr(key.key_product), key.n_queries,
-                           key.n_products, _ptr(wts), W, _ptr(flt), G, k, int(bool(allow_missing)), table.data_ptr(), key.n_queries, ws.data_ptr(), ws_bytes,
-                           _ptr(hist), _ptr(values), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+    args = (_ptr(q), _ptr(p), _ptr(mem), M, n, _ptr(key.key_query), _ptr(key.key_off), _ptr(key.key_product), key.n_queries, key.n_products, _ptr(wts), W,
+            _ptr(flt), G, k, int(bool(allow_missing)), table.data_ptr(), key.n_queries, ws.data_ptr(), ws_bytes, _ptr(hist), _ptr(values))
+    if want_codes:
+        codes = torch.empty((G, key.n_queries, (W + 63) // 64 * 64), dtype=torch.uint8, device=dev)
+        rc = l.mms_joint_sweep_codes(*args, _ptr(codes), codes.numel(), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
+        _check_rc(l, rc, "mms_joint_sweep_codes")
+        return values, hist, status, codes
+    rc = l.mms_joint_sweep(*args, status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     _check_rc(l, rc, "mms_joint_sweep")
     return values, hist, status
+
+
+# ---- resampling the joint fit: byte codes per (vector, filter, key query) and replicates of counts over the key (mms_joint_sweep_codes,
+# mms_resample_select, csrc/resample.hip) ----
+# byte code: ideal << 5 | mask for a graded query (k <= 5: mask < 32), 0xFF for code -1 (no table rows), 0xFE for code -2 (rows but no output row)
+BYTE_MISSING, BYTE_DROPPED = 0xFF, 0xFE
+FLAG_EMPTY_FIT = 32                                                                        # status[2] bit 5 of mms_resample_select (MMS_FLAG_EMPTY_FIT)
+MAX_REPLICATES, MAX_PROBES = 1 << 16, 256                                                  # MMS_RESAMPLE_MAX_REPLICATES, MMS_RESAMPLE_MAX_PROBES
+_BYTE_TABLES: dict = {}
+
+
+def byte_codes(codes):
+    """The int32 codes of ``submission_codes`` (``mask | ideal << 8``, -1, -2) as the bytes of ``mms_joint_sweep_codes``: uint8, same shape."""
+    c = np.asarray(codes).astype(np.int64)
+    return np.where(c == CODE_MISSING, BYTE_MISSING, np.where(c == CODE_DROPPED, BYTE_DROPPED, (c >> 8) << 5 | (c & 0x1F))).astype(np.uint8)
+
+
+def byte_values(k: int = 5):
+    """float64 [256]: the nDCG@k of a key query per code byte (``_code_value`` of the byte's code) -- the table ``mms_resample_select`` takes as
+    ``byte_value``.  0.0 for the two reserved bytes and for the bytes that cannot occur at this k.  Read-only, built once per k."""
+    _filter_k(k)
+    if k not in _BYTE_TABLES:
+        t = np.zeros(256, np.float64)
+        for ideal in range(k + 1):
+            for mask in range(1 << k):
+                t[ideal << 5 | mask] = _code_value(mask | ideal << 8, k)
+        t.setflags(write=False)
+        _BYTE_TABLES[k] = t
+    return _BYTE_TABLES[k]
+
+
+def _byte_table(k, dev):
+    import torch
+    if (k, dev) not in _BYTE_TABLES:
+        _BYTE_TABLES[k, dev] = torch.from_numpy(byte_values(k).copy()).to(dev)
+    return _BYTE_TABLES[k, dev]
+
+
+def joint_codes_host(query_id, product_id, members, weights, filters, rank_label: dict, k: int = 5, allow_missing: bool = False):
+    """The host form of the code matrix of ``mms_joint_sweep_codes`` and its reference: per weight vector ``w`` and filter ``(gap, tie)`` the bytes of
+    ``submission_codes`` on ``merge_members(members, w)``.  -> uint8 numpy [W, G, Qa] (item-major: ``[v, g]`` are the codes of item ``v * G + g``)."""
+    mem = _member_array(members)
+    wts = np.asarray(weights, np.float64)
+    f = _filter_array(filters)
+    _joint_args(mem, wts, f.shape[0], k)
+    label_dict = rank_label.rank_label if isinstance(rank_label, AnswerKey) else rank_label
+    mem = mem.reshape(mem.shape[0], -1)
+    out = np.empty((wts.shape[0], f.shape[0], len(label_dict)), np.uint8)
+    for v in range(wts.shape[0]):
+        merged = merge_members(mem, wts[v])
+        for g in range(f.shape[0]):
+            out[v, g] = byte_codes(submission_codes(query_id, product_id, merged, label_dict, f[g, 0], f[g, 1], k, allow_missing))
+    return out
+
+
+def _count_arrays(count_fit, count_eval, n_key_queries):
+    cf, ce = np.ascontiguousarray(count_fit), np.ascontiguousarray(count_eval)
+    if cf.dtype != np.uint8 or ce.dtype != np.uint8 or cf.ndim != 2 or cf.shape != ce.shape or cf.shape[1] != n_key_queries:
+        raise ValueError("count_fit / count_eval must be uint8 [R, %d], not %s %s / %s %s" % (n_key_queries, cf.dtype, cf.shape, ce.dtype, ce.shape))
+    if cf.shape[0] > MAX_REPLICATES:
+        raise ValueError("at most %d replicates per call" % MAX_REPLICATES)
+    return cf, ce
+
+
+def _probe_array(probes):
+    pr = np.zeros(0, np.int64) if probes is None else np.ascontiguousarray(probes, np.int64).reshape(-1)
+    if pr.shape[0] > MAX_PROBES:
+        raise ValueError("at most %d probes per call" % MAX_PROBES)
+    return pr
+
+
+def resample_select_host(codes, count_fit, count_eval, k: int = 5, probes=None, block: int = 16):
+    """The host form of ``mms_resample_select`` and its reference.  ``codes``: uint8 [W, G, Qa] (``joint_codes_host``); ``count_fit`` / ``count_eval``:
+    uint8 [R, Qa]; ``probes``: items ``v * G + g``.  Per replicate r and item
+    ``fit = (sum_i float64(count_fit[r, i]) * byte_values(k)[code[item, i]]) / float64(sum_i count_fit[r, i])`` -- the loop over i outermost, the
+    product and the sum numpy operations of their own (rounded on their own) --, the FIRST item at the maximum, and the same sum with ``count_eval``
+    on the winner and on the probes.  A fit row that sums to zero: winner -1, NaN values.  -> (best int64 [R], fit_value [R], eval_value [R],
+    probe_fit [R, P], probe_eval [R, P]), numpy.  ``block``: replicates per pass (memory only: the result does not depend on it)."""
+    c = np.asarray(codes)
+    if c.dtype != np.uint8 or c.ndim != 3:
+        raise ValueError("codes must be uint8 [W, G, Qa], not %s %s" % (c.dtype, c.shape))
+    W, G, Qa = c.shape
+    cf, ce = _count_arrays(count_fit, count_eval, Qa)
+    pr = _probe_array(probes)
+    R, P, items = cf.shape[0], pr.shape[0], W * G
+    vals = byte_values(k)[c.reshape(items, Qa)]                               # [items, Qa]
+    sum_f, sum_e = cf.sum(1, dtype=np.int64).astype(np.float64), ce.sum(1, dtype=np.int64).astype(np.float64)
+    best = np.full(R, -1, np.int64)
+    fit_value, eval_value = np.full(R, np.nan), np.full(R, np.nan)
+    probe_fit, probe_eval = np.full((R, P), np.nan), np.full((R, P), np.nan)
+
+    def sums_on(rows, count, item):                                          # the sequential sum of replicates `rows` on their items `item` [len(rows)]
+        acc = np.zeros(len(rows), np.float64)
+        for i in range(Qa):
+            prod = count[rows, i].astype(np.float64) * vals[item, i]
+            acc = acc + prod
+        return acc
+
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for r0 in range(0, R, block):
+            rows = np.arange(r0, min(R, r0 + block))
+            if items:
+                acc = np.zeros((len(rows), items), np.float64)
+                for i in range(Qa):
+                    prod = cf[rows, i].astype(np.float64)[:, None] * vals[None, :, i]
+                    acc = acc + prod
+                fit = acc / sum_f[rows, None]
+                ok = sum_f[rows] > 0
+                b = np.argmax(np.where(ok[:, None], fit, 0.0), axis=1)      # the first item at the maximum
+                best[rows[ok]] = b[ok]
+                fit_value[rows[ok]] = fit[ok, b[ok]]
+                eval_value[rows[ok]] = sums_on(rows[ok], ce, b[ok]) / sum_e[rows[ok]]
+            for j, it in enumerate(pr.tolist()):
+                if 0 <= it < items:
+                    item = np.full(len(rows), it, np.int64)
+                    probe_fit[rows, j] = sums_on(rows, cf, item) / sum_f[rows]
+                    probe_eval[rows, j] = sums_on(rows, ce, item) / sum_e[rows]
+    return best, fit_value, eval_value, probe_fit, probe_eval
+
+
+def joint_codes_device(query_id, product_id, members, weights, filters, rank_label, k: int = 5, allow_missing: bool = False, want_hist: bool = False,
+                       chunk_tiles: int = None):
+    """``mms_joint_sweep_codes``: ``joint_sweep_device`` that keeps the per-query codes.  -> (values float64 [W, G], hist or None, status int32 [4],
+    codes uint8 [G, Qa, Wp] with Wp = 64 * ceil(W / 64)), device tensors; ``codes[g, i, v]`` equals ``joint_codes_host(..)[v, g, i]`` for v < W while
+    the flag word is clean, and values / hist / status are those of ``joint_sweep_device``, bit for bit.  Only enqueues on the current stream."""
+    return _joint_sweep_call(query_id, product_id, members, weights, filters, rank_label, k, allow_missing, want_hist, chunk_tiles, True)
+
+
+def resample_select_device(codes, n_weights: int, count_fit, count_eval, k: int = 5, probes=None, status=None):
+    """``mms_resample_select`` on the device codes of ``joint_codes_device`` (uint8 [G, Qa, Wp]) for the first ``n_weights`` vectors.  ``count_fit`` /
+    ``count_eval``: uint8 [R, Qa] (device tensors are used in place, host arrays copied up once); ``probes``: items ``v * G + g``, a host list or an
+    int64 device tensor; ``status``: the int32 [4] device block to OR the flags into (default: a zeroed one; pass the sweep's to read every flag at
+    once).  -> (best int64 [R], fit_value [R], eval_value [R], probe_fit [R, P], probe_eval [R, P], status), device tensors, equal to
+    ``resample_select_host`` -- winners entry for entry, values bit for bit.  Only enqueues on the current stream."""
+    import torch
+
+    from . import lib as _lib
+    _filter_k(k)
+    if not torch.is_tensor(codes) or codes.dtype != torch.uint8 or codes.ndim != 3 or not codes.is_cuda or not codes.is_contiguous():
+        raise ValueError("codes must be the contiguous uint8 [G, Qa, Wp] device tensor of joint_codes_device")
+    dev = codes.device
+    G, Qa, Wp = codes.shape
+    W = int(n_weights)
+    if W < 0 or Wp != (W + 63) // 64 * 64:
+        raise ValueError("resample_select_device: %d weight vectors do not match codes of %s" % (W, tuple(codes.shape)))
+    to_u8 = lambda x: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).to(dev, non_blocking=True).contiguous()
+    cf, ce = to_u8(count_fit), to_u8(count_eval)
+    if cf.dtype != torch.uint8 or ce.dtype != torch.uint8 or cf.ndim != 2 or cf.shape != ce.shape or cf.shape[1] != Qa:
+        raise ValueError("count_fit / count_eval must be uint8 [R, %d], not %s %s / %s %s" % (Qa, cf.dtype, tuple(cf.shape), ce.dtype, tuple(ce.shape)))
+    R = cf.shape[0]
+    pr = probes if torch.is_tensor(probes) else torch.from_numpy(_probe_array(probes))
+    pr = pr.to(device=dev, dtype=torch.int64, non_blocking=True).contiguous().reshape(-1)
+    P = pr.shape[0]
+    if R > MAX_REPLICATES or P > MAX_PROBES:
+        raise ValueError("at most %d replicates and %d probes per call" % (MAX_REPLICATES, MAX_PROBES))
+    l = _lib.load()
+    ws_bytes = l.mms_resample_workspace_bytes(W, G, Qa, R)
+    if ws_bytes < 0:
+        raise ValueError("resample_select_device: %d x %d items, %d key queries, %d replicates: beyond the limits of mms_resample_select" % (W, G, Qa, R))
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    if status is None:
+        status = torch.zeros((4,), dtype=torch.int32, device=dev)
+    best = torch.empty((R,), dtype=torch.int64, device=dev)
+    fit_value, eval_value = (torch.empty((R,), dtype=torch.float64, device=dev) for _ in range(2))
+    probe_fit, probe_eval = (torch.empty((R, P), dtype=torch.float64, device=dev) for _ in range(2))
+    rc = l.mms_resample_select(_ptr(codes), codes.numel(), W, G, Qa, _ptr(cf), _ptr(ce), R, _byte_table(k, dev).data_ptr(), _ptr(pr), P, ws.data_ptr(),
+                               ws_bytes, _ptr(best), _ptr(fit_value), _ptr(eval_value), _ptr(probe_fit), _ptr(probe_eval), status.data_ptr(),
+                               torch.cuda.current_stream(dev).cuda_stream)
+    _check_rc(l, rc, "mms_resample_select")
+    return best, fit_value, eval_value, probe_fit, probe_eval, status

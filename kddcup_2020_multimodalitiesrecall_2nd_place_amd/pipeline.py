@@ -519,6 +519,23 @@ class EnsembleScorer:
             scores_out.update(query_id=qid, product_id=pid, members=mem)
         return ensemble.fit_joint(qid, pid, mem, rank_label, grid, filters, k, info=info)
 
+    def fit_joint_resampled_tsv_native(self, tsv_path, vocab_path, label_table, rank_label, grid=None, filters=None, k: int = 5, labels: str = "answer",
+                                       batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host", info: dict = None, scores_out: dict = None,
+                                       **resample):
+        """``fit_joint_tsv_native`` AND the held-out estimate of its winner: ONE pass as there, then ``ensemble.fit_joint_resampled`` on the member
+        scores left on the device (``mms_joint_sweep_codes`` + ``mms_resample_select``, one synchronising read).  ``resample``: its keywords
+        (``scheme``, ``folds``, ``repeats``, ``replicates``, ``seed``, ``counts``, ``probes``, ``code_budget``).  -> the dict of
+        ``fit_joint_resampled``: ``whole`` is the tuple of ``fit_joint_tsv_native``; ``heldout``, ``optimism`` and ``agreement`` say how far to trust
+        it.  The scorer's own weights are NOT changed.  ``scores_out`` as in ``fit_joint_tsv_native``."""
+        from . import ensemble
+        _check_eval_args("device", labels)
+        rank_label, relabel = _relabel(labels, rank_label, self.zk.device)
+        qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=True, relabel=relabel)
+        mem = torch.cat([m for _, m in out], 1) if out else torch.zeros((4, 0), dtype=torch.float32, device=self.zk.device)
+        if scores_out is not None:
+            scores_out.update(query_id=qid, product_id=pid, members=mem)
+        return ensemble.fit_joint_resampled(qid, pid, mem, rank_label, grid, filters, k, info=info, **resample)
+
     def score_tsv_native(self, tsv_path, vocab_path, label_table, batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host"):
         """``score_lines`` on a TSV file through libmmfeat, decode and scoring overlapped: a producer thread decodes span batch i+1
         three times (zk flavour, zk with the sen2forest rewrite, lxmert flavour; ctypes releases the GIL, each featurizer rotates
