@@ -174,11 +174,11 @@ typedef struct mms_ensemble_batch {
 /* ABI revision of the structs and entry points declared in this header.  It changes whenever a struct gains a field or an entry
  * point changes its signature (r1: 1; r2 added mms_config.fuse_layernorm, mms_zk_batch.label_ids, mms_lxmert_batch.label_ids / x_norm
  * without bumping it; r3: 3, then 4 with mms_config.fuse_attention; r4: 5 -- mms_dbg_gemm takes the engine per call,
- * the process-global mms_set_gemm_variant and the lab engines' hooks left the product library, fuse_layernorm became a mask; r5: 6 -- mms_dbg_qkv_attn and mms_side_lane_flops added; r7: 7 -- mms_decode_feats_b64 added; r8: 8 -- mms_rank_workspace_bytes and mms_rank_submission added; r9: 9 -- mms_ndcg_workspace_bytes, mms_key_relevance and mms_ndcg_at_k added; r10: 10 -- mms_ndcg_sweep_workspace_bytes and mms_ndcg_weight_sweep added; r11: 11 -- mms_filter_sweep_workspace_bytes and mms_filter_sweep added; r12: 12 -- mms_joint_sweep_workspace_bytes and mms_joint_sweep added; r13: 13 -- mms_joint_sweep_codes, mms_resample_workspace_bytes and mms_resample_select added).  A caller built against another revision would make the library read past its structs, so compare
+ * the process-global mms_set_gemm_variant and the lab engines' hooks left the product library, fuse_layernorm became a mask; r5: 6 -- mms_dbg_qkv_attn and mms_side_lane_flops added; r7: 7 -- mms_decode_feats_b64 added; r8: 8 -- mms_rank_workspace_bytes and mms_rank_submission added; r9: 9 -- mms_ndcg_workspace_bytes, mms_key_relevance and mms_ndcg_at_k added; r10: 10 -- mms_ndcg_sweep_workspace_bytes and mms_ndcg_weight_sweep added; r11: 11 -- mms_filter_sweep_workspace_bytes and mms_filter_sweep added; r12: 12 -- mms_joint_sweep_workspace_bytes and mms_joint_sweep added; r13: 13 -- mms_joint_sweep_codes, mms_resample_workspace_bytes and mms_resample_select added; r14: 14 -- mms_cascade_workspace_bytes, mms_cascade_select and mms_score_ensemble_cascade added).  A caller built against another revision would make the library read past its structs, so compare
  * BEFORE the first mms_create:  if (mms_version() != MMS_ABI_VERSION) abort();   (lib.py's load() does) */
-#define MMS_ABI_VERSION 13
+#define MMS_ABI_VERSION 14
 int mms_version(void);
-const char* mms_global_error(void);              /* message of the last failing mms_create / mms_decode_feats_b64 / mms_rank_submission / mms_key_relevance / mms_ndcg_at_k / mms_ndcg_weight_sweep / mms_filter_sweep / mms_joint_sweep / mms_joint_sweep_codes / mms_resample_select */
+const char* mms_global_error(void);              /* message of the last failing mms_create / mms_decode_feats_b64 / mms_rank_submission / mms_key_relevance / mms_ndcg_at_k / mms_ndcg_weight_sweep / mms_filter_sweep / mms_joint_sweep / mms_joint_sweep_codes / mms_resample_select / mms_cascade_select */
 
 int mms_create(const mms_config* cfg, mms_handle** out);
 void mms_destroy(mms_handle* h);
@@ -238,6 +238,59 @@ int mms_score_lxmert(mms_handle* h, const mms_lxmert_batch* b, float* logits, fl
  * main.py reads from the score files).  The three handles must live on the same device; zk and lds share text_len. */
 int mms_score_ensemble(mms_handle* zk, mms_handle* lds, mms_handle* lxmert, const mms_ensemble_batch* b, const float* weights4,
                        float* merged, float* member_scores, void* stream);
+
+/* Cascade form of mms_score_ensemble (opt-in, approximate by construction): the cheapest member prunes, the other three score what is left.
+ * Inputs are those of mms_score_ensemble plus group_ids [B] (device int64: the query id of each pair; rows of a query need not be adjacent;
+ * MMS_RANK_RESERVED_ID is reserved) and keep >= 1.
+ *   Stage 1.  x[i] = the lxmert member's score, softmax(logit)[1], of EVERY pair, computed exactly as mms_score_ensemble computes member 3 for the
+ *     same batch: bit-equal to member 3 of mms_score_ensemble on the same feed (and to mms_score_lxmert wherever the text above promises that).
+ *   Selection (mms_cascade_select).  Within each query the rows are ordered by (x descending, row index ascending); -0.0 == +0.0: the comparison
+ *     is made on the fp32 value widened exactly to double.  The first min(keep, rows) rows of that order are KEPT.  kept_list holds the kept row
+ *     indices in ascending row order, n_kept is their number.
+ *   Stage 2.  The kept rows are gathered, in kept_list order, into a batch of their own (a device copy of the eleven arrays of mms_ensemble_batch,
+ *     the box features in 16-byte accesses), and members 0, 1, 2 are computed for it.  BIT-EQUALITY RULE: they are bit-equal to what
+ *     mms_score_ensemble returns for that gathered batch passed as a call of its own -- the label de-duplication runs over the kept pairs, the launch
+ *     waves, size regimes, lanes and LayerNorm route are those of a batch of n_kept pairs; nothing of stage 1 is reused.
+ *   Output.   member_scores[0..2][i] = the stage-2 score of a kept pair, exactly 0.0f for a pruned pair; member_scores[3][i] = x[i] for both.
+ *     merged[i] = ((w0 * m0 + w1 * m1) + w2 * m2) + w3 * m3 on these four values, every product and sum rounded to fp32 on its own (the merge of
+ *     mms_score_ensemble); for a pruned pair that is ((w0 * 0 + w1 * 0) + w2 * 0) + w3 * x[i].  kept[i] (device uint8 [B]) = 1 / 0; *n_kept_out
+ *     (host, optional) = the number of kept pairs.
+ *   ORDERING GUARANTEE.  For non-negative weights and member scores in [0, 1], every kept pair of a query has merged >= every pruned pair of the same
+ *     query: x(kept) >= x(pruned) by the selection, the other three terms are >= 0, and fp32 rounding is monotone.  The per-query top of `merged`
+ *     therefore consists of kept pairs as long as the query has that many.
+ *   Batch boundaries.  The call sees one batch: a query that the caller cuts across two calls is selected per part, and the union of the parts'
+ *     selections contains the whole-query selection -- never fewer pairs kept than specified, only (rarely) more.
+ *   Flags (first status word of mms_cascade_select): a non-finite x, a group id equal to MMS_RANK_RESERVED_ID, B > MMS_CASCADE_MAX_ROWS.  On any flag
+ *     EVERY pair is kept, i.e. the call returns the full ensemble result (detected, served by the exact form).  With keep >= the rows of the largest
+ *     query the result equals mms_score_ensemble's bit for bit, merged and member_scores.
+ *   Cost.  Two label de-duplication read-backs (one per stage) and the second zk member's count read, as in mms_score_ensemble, plus ONE 16-byte device ->
+ *     host read of the status word between the stages.  The buffers of the gathered batch and of the selection live in the zk handle and grow on
+ *     demand: a warmed-up handle does not allocate.  The caller's current device is restored on return.
+ * Returns MMS_ERR_ARG for keep < 1, a NULL group_ids / kept with B > 0, B >= 2^31, and whatever mms_score_ensemble rejects. */
+int mms_score_ensemble_cascade(mms_handle* zk, mms_handle* lds, mms_handle* lxmert, const mms_ensemble_batch* b, const int64_t* group_ids,
+                               int32_t keep, const float* weights4, float* merged, float* member_scores, uint8_t* kept, int64_t* n_kept_out,
+                               void* stream);
+
+/* The selection of the cascade alone, over two parallel device arrays of n rows (group_ids int64, score_f32): kept_u8 [n] = 1 for a kept row, 0
+ * for a pruned one; kept_list_i32 [n]: the kept rows in ascending row order (the first n_kept entries are written); semantics as above.
+ *   status: device int32 [4]:  [0] flags  [1] n_kept  [2] distinct queries  [3] rows of the largest query  ([2], [3]: over the rows without a flag)
+ *   flags:  MMS_CASCADE_FLAG_NONFINITE  a non-finite score (NaN, +-inf)      MMS_CASCADE_FLAG_RESERVED_ID  a group id equal to MMS_RANK_RESERVED_ID
+ *           MMS_CASCADE_FLAG_TOO_MANY   n > MMS_CASCADE_MAX_ROWS (nothing is ranked; [2] = [3] = 0)
+ *   With a non-zero flag word every row is kept: kept_u8 all ones, kept_list = 0 .. n - 1, n_kept = n.
+ *   workspace: device memory, 256-byte aligned, at least mms_cascade_workspace_bytes(n) bytes (no content expected, none preserved).
+ * A row is kept iff fewer than `keep` rows of its query rank before it: no sort, no limit on the rows of a query or on keep (a query of more than
+ * `keep` rows costs rows x min(rows, rank) comparisons, one wavefront per query; queries of at most `keep` rows cost none).
+ * Only integer atomics whose result does not depend on arrival order: equal inputs give equal bytes on every run.
+ * The call ONLY ENQUEUES on `stream` (three fills, nine kernels): no allocation, no synchronisation, no device -> host read.
+ * Returns MMS_ERR_ARG (message in mms_global_error, nothing launched) for n < 0 or n >= 2^31, keep < 1, a NULL status, a NULL pointer with n > 0,
+ * a workspace smaller than mms_cascade_workspace_bytes(n) or not 256-byte aligned.  n == 0 writes a zero status and returns 0.  Handle-free. */
+#define MMS_CASCADE_MAX_ROWS (1 << 22)
+#define MMS_CASCADE_FLAG_NONFINITE 1
+#define MMS_CASCADE_FLAG_RESERVED_ID 2
+#define MMS_CASCADE_FLAG_TOO_MANY 4
+int64_t mms_cascade_workspace_bytes(int64_t n);   /* a multiple of 256; -1 for n < 0 or n >= 2^31 */
+int mms_cascade_select(const int64_t* group_ids, const float* score_f32, int64_t n, int32_t keep, uint8_t* kept_u8, int32_t* kept_list_i32,
+                       int32_t* status /* [4] */, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Box features of B records from their base64 text (the TSV's 6th field: f32 [num_boxes, 2048] row-major), decoded on the device --
  * the host gathers the text (libmmfeat mmf_gather_spans) instead of decoding it, and the H2D copy carries ~42 KB per record instead of 80 KB.

@@ -144,6 +144,12 @@ struct mms_handle {
     int *ens_diff = nullptr, *ens_doff = nullptr, *ens_dlist = nullptr, *ens_dcount = nullptr;
     int32_t *ens_cq = nullptr, *ens_clen = nullptr, *ens_cnb = nullptr; int64_t* ens_clab = nullptr;
     float *ens_ctok = nullptr, *ens_clog = nullptr, *ens_cprob = nullptr; int64_t ens_cpairs = 0;
+    // mms_score_ensemble_cascade: first-stage column, kept list, status and the selection workspace (sized for cas_pairs); the gathered batch of the second stage (cas_g_pairs)
+    std::vector<void*> cas_allocs, cas_g_allocs;
+    int64_t cas_pairs = 0, cas_g_pairs = 0;
+    float* cas_x = nullptr; int32_t *cas_list = nullptr, *cas_status = nullptr; void* cas_ws = nullptr;
+    float *cas_feats = nullptr, *cas_boxes5 = nullptr; int64_t* cas_labels = nullptr;
+    int32_t *cas_nb = nullptr, *cas_lab = nullptr, *cas_q = nullptr, *cas_len = nullptr, *cas_q2 = nullptr, *cas_len2 = nullptr, *cas_lxi = nullptr, *cas_lxm = nullptr;
     Planes ens_featp; int64_t ens_featp_pairs = 0;      // the wave's split box features when the three members run side by side (they may not live in zk's FFN buffer then)
 
     // ---- gemm timing ----
@@ -2055,6 +2061,8 @@ void mms_destroy(mms_handle* h) {
     free_pool(h->dd_allocs);
     free_pool(h->ens_allocs);
     free_pool(h->ens_c_allocs);
+    free_pool(h->cas_allocs);
+    free_pool(h->cas_g_allocs);
     free_pool(h->lq_allocs);
     free_pool(h->lq_sub_allocs);
     if (h->lq_store.hi) (void)hipFree(h->lq_store.hi);
@@ -2207,8 +2215,8 @@ static int ensure_ens_ws(mms_handle* z, int64_t B, int T, int TL) {
     return MMS_OK;
 }
 
-int mms_score_ensemble(mms_handle* z, mms_handle* l, mms_handle* x, const mms_ensemble_batch* b, const float* weights4, float* merged,
-                       float* member_scores, void* stream) {
+// the argument checks of the two ensemble entry points (B == 0 passes: the caller returns before anything is read)
+static int ens_check(mms_handle* z, mms_handle* l, mms_handle* x, const mms_ensemble_batch* b, const float* weights4, const float* merged) {
     if (!z || !l || !x) return MMS_ERR_ARG;
     if (int rc = check_ready(z, MMS_MODEL_ZK, b, merged)) return rc;
     if (int rc = check_ready(l, MMS_MODEL_LDS, b, merged)) return z->fail(rc, "lds handle: " + l->err);
@@ -2222,8 +2230,17 @@ int mms_score_ensemble(mms_handle* z, mms_handle* l, mms_handle* x, const mms_en
     if (!weights4 || !b->feats || !b->boxes_5 || !b->num_boxes || !b->label_ids || !b->query_ids || !b->len_query || !b->s2f_query_ids ||
         !b->s2f_len_query || !b->labels || !b->lx_input_ids || !b->lx_input_mask)
         return z->fail(MMS_ERR_ARG, "mms_score_ensemble: null batch field");
-    DeviceScope dev(z->cfg.device);
-    hipStream_t st = (hipStream_t)stream;
+    return MMS_OK;
+}
+
+// The members named by `members` (ENS_ZK: both zk members, ENS_LDS, ENS_LX) on the pairs of b, B > 0, on the handles' device: probs[k] points at member k's
+// [B,2] probabilities (in zk's ensemble buffers; valid for the members that ran, until the next ensemble call).  Everything that decides a launch's regime -- the wave
+// size, the lanes, the LayerNorm route -- is decided by B and the three handles alone, never by the mask, and a member's launches do not depend on which other members
+// run: ENS_ALL is the launch sequence of mms_score_ensemble, and a subset computes its members bit for bit as ENS_ALL does on the same batch.
+enum { ENS_ZK = 1, ENS_LDS = 2, ENS_LX = 4, ENS_ALL = 7 };
+static int ens_run(mms_handle* z, mms_handle* l, mms_handle* x, const mms_ensemble_batch* b, unsigned members, hipStream_t st, const float* probs[4]) {
+    const int64_t B = b->n_pairs;
+    const bool do_z = members & ENS_ZK, do_l = members & ENS_LDS, do_x = members & ENS_LX;
     const int T = z->cfg.text_len, TL = x->cfg.text_len;
     // one launch-wave size for the three members (the smallest of their chunk settings)
     int cs = chunk_size(z, B);
@@ -2236,21 +2253,25 @@ int mms_score_ensemble(mms_handle* z, mms_handle* l, mms_handle* x, const mms_en
     if (int rc = ln_begin_call(l, st)) return z->fail(rc, "lds handle: " + l->err);
     if (int rc = ln_begin_call(x, st)) return z->fail(rc, "lxmert handle: " + x->err);
     // ---- feeds in each member's own dtypes ----
-    launch_zk_segment_ids(z->ens_seg, B, T, st);                                   // load_data_v4.py:204
-    launch_i32_to_i64(b->query_ids, z->ens_ids64, B * T, st);                      // lds reads the zk query as int64 (run_pretraining_predict_score.py:526-548)
-    launch_fill_i64(z->ens_seg64, B * T, 0, st);
-    launch_i32_to_i64(b->label_ids, z->ens_lab64, B * MMS_NBOX * MMS_LABEL_LEN, st);
+    if (do_z) launch_zk_segment_ids(z->ens_seg, B, T, st);                         // load_data_v4.py:204
+    if (do_l) {
+        launch_i32_to_i64(b->query_ids, z->ens_ids64, B * T, st);                  // lds reads the zk query as int64 (run_pretraining_predict_score.py:526-548)
+        launch_fill_i64(z->ens_seg64, B * T, 0, st);
+        launch_i32_to_i64(b->label_ids, z->ens_lab64, B * MMS_NBOX * MMS_LABEL_LEN, st);
+    }
     int64_t* lx_ids = z->ens_mask64;
     int64_t* lx_mask = z->ens_mask64 + B * TL;
-    launch_i32_to_i64(b->lx_input_ids, lx_ids, B * TL, st);
-    launch_i32_to_i64(b->lx_input_mask, lx_mask, B * TL, st);
-    launch_box_mask(b->num_boxes, z->ens_vmask, B, st);
-    launch_corners(b->boxes_5, z->ens_boxes4, B, st);
+    if (do_x) {
+        launch_i32_to_i64(b->lx_input_ids, lx_ids, B * TL, st);
+        launch_i32_to_i64(b->lx_input_mask, lx_mask, B * TL, st);
+        launch_box_mask(b->num_boxes, z->ens_vmask, B, st);
+        launch_corners(b->boxes_5, z->ens_boxes4, B, st);
+    }
     // ---- label text: distinct tuples once, encoded by zk's conv stack and by lxmert's label encoder ----
     int64_t U = 0;
     if (int rc = dedup_labels<int32_t>(z, st, b->label_ids, B * MMS_NBOX, &U)) return rc;
-    if (int rc = zk_label_features(z, st, z->dd_uniq32, U)) return rc;
-    if (int rc = lx_label_features(x, st, z->dd_uniq64, U)) return z->fail(rc, "lxmert handle: " + x->err);
+    if (do_z) if (int rc = zk_label_features(z, st, z->dd_uniq32, U)) return rc;
+    if (do_x) if (int rc = lx_label_features(x, st, z->dd_uniq64, U)) return z->fail(rc, "lxmert handle: " + x->err);
     const int32_t* index = z->dd_index;
 
     mms_zk_batch zb{};
@@ -2296,12 +2317,12 @@ int mms_score_ensemble(mms_handle* z, mms_handle* l, mms_handle* x, const mms_en
     x->lanes_on = x_small && !x->timing;
     x->no_fused_ln = ens_small || x_small;
     x->lanes_q = ens_lanes && x->lanes_on && lane_query_stage();
-    if (int rc = lx_query_stage(x, st, &xb, B, cs)) return z->fail(rc, "lxmert member: " + x->err);
+    if (do_x) if (int rc = lx_query_stage(x, st, &xb, B, cs)) return z->fail(rc, "lxmert member: " + x->err);
     float* lg[4]; float* pr[4];
     for (int k = 0; k < 4; ++k) { lg[k] = z->ens_logits + (int64_t)k * B * 2; pr[k] = z->ens_probs + (int64_t)k * B * 2; }
 
     // image tokens of a wave survive zk's first encoder pass in a side buffer (the QKV buffer they are built in gets reused)
-    if (!z->ens_tok) {
+    if (do_z && !z->ens_tok) {
         void* p;
         if (int rc = dev_alloc(z, z->ws_allocs, &p, (size_t)z->ws_pairs * MMS_NBOX * H * 4)) return rc;   // lives and dies with the workspace
         z->ens_tok = (float*)p;
@@ -2309,17 +2330,19 @@ int mms_score_ensemble(mms_handle* z, mms_handle* l, mms_handle* x, const mms_en
     // second zk member: the rewrite (load_data_v4.py:153-154) touches only queries that contain the phrase; every other pair's second
     // forward would repeat the first one bit for bit, so only the changed pairs are encoded again (per launch wave: flags -> scan ->
     // compact list; the per-wave counts come back in one small read)
-    launch_query_differs(b->query_ids, b->len_query, b->s2f_query_ids, b->s2f_len_query, T, (int)B, z->ens_diff, st);
     const int n_waves = (int)((B + cs - 1) / cs);
     if (n_waves > (int)(B / 64 + 16)) return z->fail(MMS_ERR_ARG, "mms_score_ensemble: chunk_pairs too small for this batch");
-    for (int wv = 0; wv < n_waves; ++wv) {
-        const int64_t p0 = (int64_t)wv * cs, n = (B - p0) < cs ? (B - p0) : cs;
-        launch_plan_scan(z->ens_diff + p0, (int)n, z->ens_doff + p0, z->ens_dcount + wv, st);
-        launch_compact_list(z->ens_diff + p0, z->ens_doff + p0, (int)n, z->ens_dlist + p0, st);
-    }
     std::vector<int> changed(n_waves);
-    HIP_TRY(z, hipMemcpyAsync(changed.data(), z->ens_dcount, (size_t)n_waves * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(z, hipStreamSynchronize(st));
+    if (do_z) {
+        launch_query_differs(b->query_ids, b->len_query, b->s2f_query_ids, b->s2f_len_query, T, (int)B, z->ens_diff, st);
+        for (int wv = 0; wv < n_waves; ++wv) {
+            const int64_t p0 = (int64_t)wv * cs, n = (B - p0) < cs ? (B - p0) : cs;
+            launch_plan_scan(z->ens_diff + p0, (int)n, z->ens_doff + p0, z->ens_dcount + wv, st);
+            launch_compact_list(z->ens_diff + p0, z->ens_doff + p0, (int)n, z->ens_dlist + p0, st);
+        }
+        HIP_TRY(z, hipMemcpyAsync(changed.data(), z->ens_dcount, (size_t)n_waves * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(z, hipStreamSynchronize(st));
+    }
     {
         int64_t need = 0;
         for (int v : changed) need = v > need ? v : need;
@@ -2355,39 +2378,155 @@ int mms_score_ensemble(mms_handle* z, mms_handle* l, mms_handle* x, const mms_en
             st_l = l->side; st_x = z->side;
             z->lane_forks += 1;
             HIP_TRY(z, hipEventRecord(z->ev_fork, st));
-            HIP_TRY(z, hipStreamWaitEvent(st_l, z->ev_fork, 0));
-            HIP_TRY(z, hipStreamWaitEvent(st_x, z->ev_fork, 0));
+            if (do_l) HIP_TRY(z, hipStreamWaitEvent(st_l, z->ev_fork, 0));
+            if (do_x) HIP_TRY(z, hipStreamWaitEvent(st_x, z->ev_fork, 0));
         }
-        if (int rc = lds_chunk(l, st_l, &lb, p0, n, lg[2], pr[2], &featp)) return z->fail(rc, "lds member: " + l->err);
-        if (int rc = lx_chunk(x, st_x, &xb, index, p0, n, lg[3], pr[3], &featp)) return z->fail(rc, "lxmert member: " + x->err);
-        if (int rc = zk_image_tokens(z, st, &zb, index, p0, n, &featp)) return rc;
-        HIP_TRY(z, hipMemcpyAsync(z->ens_tok, z->qkv + NB * H, (size_t)NB * H * 4, hipMemcpyDeviceToDevice, st));
-        if (int rc = zk_encode(z, st, &zb, p0, n, z->ens_tok, lg[0], pr[0])) return rc;
-        const int64_t n2 = changed[p0 / cs];
-        if (n2 > 0) {   // the changed pairs of this wave, compacted: rewritten query + their rows of the shared image tokens
-            const int* list = z->ens_dlist + p0;
-            launch_gather_rows_i32(b->s2f_query_ids + p0 * T, list, T, n2, z->ens_cq, st);
-            launch_gather_rows_i32(b->s2f_len_query + p0, list, 1, n2, z->ens_clen, st);
-            launch_gather_rows_i32(b->num_boxes + p0, list, 1, n2, z->ens_cnb, st);
-            launch_gather_rows_i64(b->labels + p0, list, 1, n2, z->ens_clab, st);
-            launch_gather_rows_f32x4(z->ens_tok, list, MMS_NBOX * H, n2, z->ens_ctok, st);
-            mms_zk_batch zc = zb2;
-            zc.n_pairs = n2; zc.query_ids = z->ens_cq; zc.len_query = z->ens_clen; zc.num_boxes = z->ens_cnb; zc.labels = z->ens_clab;
-            zc.segment_ids = z->ens_seg;                                  // the same 0 x T, 1 x 10 pattern for every pair
-            if (int rc = zk_encode(z, st, &zc, 0, n2, z->ens_ctok, z->ens_clog, z->ens_cprob)) return rc;
+        if (do_l) if (int rc = lds_chunk(l, st_l, &lb, p0, n, lg[2], pr[2], &featp)) return z->fail(rc, "lds member: " + l->err);
+        if (do_x) if (int rc = lx_chunk(x, st_x, &xb, index, p0, n, lg[3], pr[3], &featp)) return z->fail(rc, "lxmert member: " + x->err);
+        if (do_z) {
+            if (int rc = zk_image_tokens(z, st, &zb, index, p0, n, &featp)) return rc;
+            HIP_TRY(z, hipMemcpyAsync(z->ens_tok, z->qkv + NB * H, (size_t)NB * H * 4, hipMemcpyDeviceToDevice, st));
+            if (int rc = zk_encode(z, st, &zb, p0, n, z->ens_tok, lg[0], pr[0])) return rc;
+            const int64_t n2 = changed[p0 / cs];
+            if (n2 > 0) {   // the changed pairs of this wave, compacted: rewritten query + their rows of the shared image tokens
+                const int* list = z->ens_dlist + p0;
+                launch_gather_rows_i32(b->s2f_query_ids + p0 * T, list, T, n2, z->ens_cq, st);
+                launch_gather_rows_i32(b->s2f_len_query + p0, list, 1, n2, z->ens_clen, st);
+                launch_gather_rows_i32(b->num_boxes + p0, list, 1, n2, z->ens_cnb, st);
+                launch_gather_rows_i64(b->labels + p0, list, 1, n2, z->ens_clab, st);
+                launch_gather_rows_f32x4(z->ens_tok, list, MMS_NBOX * H, n2, z->ens_ctok, st);
+                mms_zk_batch zc = zb2;
+                zc.n_pairs = n2; zc.query_ids = z->ens_cq; zc.len_query = z->ens_clen; zc.num_boxes = z->ens_cnb; zc.labels = z->ens_clab;
+                zc.segment_ids = z->ens_seg;                                  // the same 0 x T, 1 x 10 pattern for every pair
+                if (int rc = zk_encode(z, st, &zc, 0, n2, z->ens_ctok, z->ens_clog, z->ens_cprob)) return rc;
+            }
+            launch_select_rows2(z->ens_diff + p0, z->ens_doff + p0, lg[0] + p0 * 2, z->ens_clog, (int)n, lg[1] + p0 * 2, st);
+            launch_select_rows2(z->ens_diff + p0, z->ens_doff + p0, pr[0] + p0 * 2, z->ens_cprob, (int)n, pr[1] + p0 * 2, st);
         }
-        launch_select_rows2(z->ens_diff + p0, z->ens_doff + p0, lg[0] + p0 * 2, z->ens_clog, (int)n, lg[1] + p0 * 2, st);
-        launch_select_rows2(z->ens_diff + p0, z->ens_doff + p0, pr[0] + p0 * 2, z->ens_cprob, (int)n, pr[1] + p0 * 2, st);
         if (ens_lanes) {      // the next wave's feature split and the merge wait for the other two members
-            HIP_TRY(z, hipEventRecord(l->ev_join, st_l));
-            HIP_TRY(z, hipStreamWaitEvent(st, l->ev_join, 0));
-            HIP_TRY(z, hipEventRecord(z->ev_join, st_x));
-            HIP_TRY(z, hipStreamWaitEvent(st, z->ev_join, 0));
+            if (do_l) { HIP_TRY(z, hipEventRecord(l->ev_join, st_l)); HIP_TRY(z, hipStreamWaitEvent(st, l->ev_join, 0)); }
+            if (do_x) { HIP_TRY(z, hipEventRecord(z->ev_join, st_x)); HIP_TRY(z, hipStreamWaitEvent(st, z->ev_join, 0)); }
         }
     }
-    const float* prc[4] = {pr[0], pr[1], pr[2], pr[3]};
-    launch_merge4(prc, weights4, merged, member_scores, B, st);
+    for (int k = 0; k < 4; ++k) probs[k] = pr[k];
     return guard.done(post_launch(z));
+}
+
+int mms_score_ensemble(mms_handle* z, mms_handle* l, mms_handle* x, const mms_ensemble_batch* b, const float* weights4, float* merged,
+                       float* member_scores, void* stream) {
+    if (int rc = ens_check(z, l, x, b, weights4, merged)) return rc;
+    const int64_t B = b->n_pairs;
+    if (B == 0) return MMS_OK;
+    DeviceScope dev(z->cfg.device);
+    hipStream_t st = (hipStream_t)stream;
+    const float* pr[4];
+    if (int rc = ens_run(z, l, x, b, ENS_ALL, st, pr)) return rc;
+    launch_merge4(pr, weights4, merged, member_scores, B, st);
+    return post_launch(z);
+}
+
+int64_t mms_cascade_workspace_bytes(int64_t n) {
+    return n < 0 || n > INT32_MAX ? -1 : (int64_t)cascade_workspace_bytes(n);
+}
+
+int mms_cascade_select(const int64_t* group_ids, const float* score_f32, int64_t n, int32_t keep, uint8_t* kept_u8, int32_t* kept_list_i32, int32_t* status,
+                       void* workspace, int64_t workspace_bytes, void* stream) {
+    if (n < 0 || n > INT32_MAX) { g_err = "mms_cascade_select: n must be in [0, 2^31)"; return MMS_ERR_ARG; }
+    if (keep < 1) { g_err = "mms_cascade_select: keep must be >= 1"; return MMS_ERR_ARG; }
+    if (!status) { g_err = "mms_cascade_select: null status"; return MMS_ERR_ARG; }
+    if (n > 0) {
+        if (!group_ids || !score_f32 || !kept_u8 || !kept_list_i32 || !workspace) { g_err = "mms_cascade_select: null pointer"; return MMS_ERR_ARG; }
+        if (reinterpret_cast<uintptr_t>(workspace) & 255) { g_err = "mms_cascade_select: workspace must be 256-byte aligned"; return MMS_ERR_ARG; }
+        if (workspace_bytes < (int64_t)cascade_workspace_bytes(n)) { g_err = "mms_cascade_select: workspace smaller than mms_cascade_workspace_bytes(n)"; return MMS_ERR_ARG; }
+    }
+    // (only enqueues: three fills and nine kernels; no allocation, no synchronisation, nothing read back)
+    launch_cascade_select(group_ids, score_f32, n, keep, kept_u8, kept_list_i32, status, workspace, (hipStream_t)stream);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { g_err = std::string("mms_cascade_select: ") + hipGetErrorString(e); return MMS_ERR_HIP; }
+    return 0;
+}
+
+// buffers of the cascade that scale with the call (B pairs) and with the second stage (n_kept pairs): both grow on demand and are kept
+static int ensure_cas_ws(mms_handle* z, int64_t B) {
+    if (B <= z->cas_pairs) return MMS_OK;
+    free_pool(z->cas_allocs);
+    z->cas_pairs = 0;
+    void* p;
+    auto get = [&](size_t bytes, void** out) { int rc = dev_alloc(z, z->cas_allocs, &p, bytes); *out = p; return rc; };
+    if (int rc = get((size_t)B * 4, (void**)&z->cas_x)) return rc;
+    if (int rc = get((size_t)B * 4, (void**)&z->cas_list)) return rc;
+    if (int rc = get(16, (void**)&z->cas_status)) return rc;
+    if (int rc = get((size_t)cascade_workspace_bytes(B), &z->cas_ws)) return rc;
+    z->cas_pairs = B;
+    return MMS_OK;
+}
+static int ensure_cas_gather(mms_handle* z, int64_t n, int T, int TL) {
+    if (n <= z->cas_g_pairs) return MMS_OK;
+    free_pool(z->cas_g_allocs);
+    z->cas_g_pairs = 0;
+    void* p;
+    auto get = [&](size_t bytes, void** out) { int rc = dev_alloc(z, z->cas_g_allocs, &p, bytes); *out = p; return rc; };
+    if (int rc = get((size_t)n * MMS_NBOX * MMS_FEAT * 4, (void**)&z->cas_feats)) return rc;
+    if (int rc = get((size_t)n * MMS_NBOX * 5 * 4, (void**)&z->cas_boxes5)) return rc;
+    if (int rc = get((size_t)n * 4, (void**)&z->cas_nb)) return rc;
+    if (int rc = get((size_t)n * MMS_NBOX * MMS_LABEL_LEN * 4, (void**)&z->cas_lab)) return rc;
+    if (int rc = get((size_t)n * T * 4, (void**)&z->cas_q)) return rc;
+    if (int rc = get((size_t)n * 4, (void**)&z->cas_len)) return rc;
+    if (int rc = get((size_t)n * T * 4, (void**)&z->cas_q2)) return rc;
+    if (int rc = get((size_t)n * 4, (void**)&z->cas_len2)) return rc;
+    if (int rc = get((size_t)n * 8, (void**)&z->cas_labels)) return rc;
+    if (int rc = get((size_t)n * TL * 4, (void**)&z->cas_lxi)) return rc;
+    if (int rc = get((size_t)n * TL * 4, (void**)&z->cas_lxm)) return rc;
+    z->cas_g_pairs = n;
+    return MMS_OK;
+}
+
+int mms_score_ensemble_cascade(mms_handle* z, mms_handle* l, mms_handle* x, const mms_ensemble_batch* b, const int64_t* group_ids, int32_t keep,
+                               const float* weights4, float* merged, float* member_scores, uint8_t* kept, int64_t* n_kept_out, void* stream) {
+    if (int rc = ens_check(z, l, x, b, weights4, merged)) return rc;
+    const int64_t B = b->n_pairs;
+    if (keep < 1) return z->fail(MMS_ERR_ARG, "mms_score_ensemble_cascade: keep must be >= 1");
+    if (B > INT32_MAX) return z->fail(MMS_ERR_ARG, "mms_score_ensemble_cascade: too many pairs in one call");
+    if (n_kept_out) *n_kept_out = 0;
+    if (B == 0) return MMS_OK;
+    if (!group_ids || !kept) return z->fail(MMS_ERR_ARG, "mms_score_ensemble_cascade: null group_ids / kept");
+    DeviceScope dev(z->cfg.device);
+    hipStream_t st = (hipStream_t)stream;
+    const int T = z->cfg.text_len, TL = x->cfg.text_len;
+    if (int rc = ensure_cas_ws(z, B)) return rc;
+    // ---- stage 1: the lxmert member on every pair, exactly as mms_score_ensemble computes it; selection on its scores ----
+    const float* pr[4];
+    if (int rc = ens_run(z, l, x, b, ENS_LX, st, pr)) return rc;
+    launch_cascade_stage1(pr[3], B, z->cas_x, st);
+    launch_cascade_select(group_ids, z->cas_x, B, keep, kept, z->cas_list, z->cas_status, z->cas_ws, st);
+    int32_t status[4] = {0, 0, 0, 0};
+    HIP_TRY(z, hipMemcpyAsync(status, z->cas_status, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(z, hipStreamSynchronize(st));
+    const int64_t nk = status[1];
+    if (nk < 1 || nk > B) return z->fail(MMS_ERR_STATE, "mms_score_ensemble_cascade: selection returned an impossible count");
+    if (n_kept_out) *n_kept_out = nk;
+    // ---- stage 2: the kept pairs, in kept_list order, as a batch of their own (a copy of the eleven feed arrays; the 80 KB of box features per pair in 16-byte accesses) ----
+    if (int rc = ensure_cas_gather(z, nk, T, TL)) return rc;
+    const int* list = z->cas_list;
+    launch_gather_rows_f32x4(b->feats, list, MMS_NBOX * MMS_FEAT, nk, z->cas_feats, st);
+    launch_gather_rows_i32((const int32_t*)b->boxes_5, list, MMS_NBOX * 5, nk, (int32_t*)z->cas_boxes5, st);     // bit copies of fp32 rows of 50
+    launch_gather_rows_i32(b->num_boxes, list, 1, nk, z->cas_nb, st);
+    launch_gather_rows_i32(b->label_ids, list, MMS_NBOX * MMS_LABEL_LEN, nk, z->cas_lab, st);
+    launch_gather_rows_i32(b->query_ids, list, T, nk, z->cas_q, st);
+    launch_gather_rows_i32(b->len_query, list, 1, nk, z->cas_len, st);
+    launch_gather_rows_i32(b->s2f_query_ids, list, T, nk, z->cas_q2, st);
+    launch_gather_rows_i32(b->s2f_len_query, list, 1, nk, z->cas_len2, st);
+    launch_gather_rows_i64(b->labels, list, 1, nk, z->cas_labels, st);
+    launch_gather_rows_i32(b->lx_input_ids, list, TL, nk, z->cas_lxi, st);
+    launch_gather_rows_i32(b->lx_input_mask, list, TL, nk, z->cas_lxm, st);
+    mms_ensemble_batch g{};
+    g.n_pairs = nk; g.feats = z->cas_feats; g.boxes_5 = z->cas_boxes5; g.num_boxes = z->cas_nb; g.label_ids = z->cas_lab; g.query_ids = z->cas_q;
+    g.len_query = z->cas_len; g.s2f_query_ids = z->cas_q2; g.s2f_len_query = z->cas_len2; g.labels = z->cas_labels; g.lx_input_ids = z->cas_lxi;
+    g.lx_input_mask = z->cas_lxm;
+    const float* pr2[4];
+    if (int rc = ens_run(z, l, x, &g, ENS_ZK | ENS_LDS, st, pr2)) return rc;
+    launch_cascade_merge(pr2, list, z->cas_status + 1, kept, z->cas_x, weights4, merged, member_scores, B, st);
+    return post_launch(z);
 }
 
 int mms_gemm_timing(mms_handle* h, int32_t enable, int32_t reset, double* ms_out, int64_t* launches_out, double* flops_out) {

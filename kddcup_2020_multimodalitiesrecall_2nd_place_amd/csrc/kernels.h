@@ -341,6 +341,17 @@ void launch_joint_sweep(const int64_t* query_id, const int64_t* product_id, cons
                         const double* filters, long long n_filters, int k, int allow_missing, const double* bin_value, long long n_key_queries_total,
                         void* workspace, long long workspace_bytes, int64_t* hist_out, double* value_out, uint8_t* code_out, int32_t* status,
                         hipStream_t st);
+// cascade.hip: per-query top-`keep` of a first-stage score (mms_cascade_select checks the arguments; workspace of cascade_workspace_bytes(n) bytes, 256-byte
+// aligned).  status = {flags, kept rows, queries, rows of the largest query}.  Enqueues three fills and nine kernels on st (n > MMS_CASCADE_MAX_ROWS: one
+// kernel that keeps every row); allocates nothing, waits for nothing.
+long long cascade_workspace_bytes(long long n);
+void launch_cascade_select(const int64_t* group_ids, const float* score, long long n, int keep, uint8_t* kept, int32_t* kept_list, int32_t* status,
+                           void* workspace, hipStream_t st);
+// around the second stage of mms_score_ensemble_cascade: x[i] = probs[i][1];  the scatter of the second stage's [n_kept,2] probabilities through kept_list
+// + the merge of k_merge4 (a pruned pair: members 0-2 = 0.0f)
+void launch_cascade_stage1(const float* probs, long long n, float* x, hipStream_t st);
+void launch_cascade_merge(const float* const probs3[3], const int* kept_list, const int* n_kept_dev, const uint8_t* kept, const float* x, const float w[4],
+                          float* merged, float* members, long long n, hipStream_t st);
 // resample.hip: per replicate (a row of counts over the key queries) the first item at the maximum of the count-weighted mean of the byte codes' values
 // (mms_resample_select checks the arguments).  Enqueues four kernels on st; allocates nothing, waits for nothing.
 long long resample_workspace_bytes(long long n_weights, long long n_filters, long long n_key_queries, long long n_replicates);

@@ -482,3 +482,113 @@ def fit_joint_resampled(query_id, product_id, members, rank_label, grid=None, fi
     return dict(whole=whole, winners=winners, fit_values=fit_values, eval_values=eval_values, probe_fit=probe_fit, probe_eval=probe_eval,
                 probes=[(iw, ig)] + probes, count_fit=count_fit, count_eval=count_eval, heldout=heldout, optimism=optimism,
                 agreement=float(np.mean(best == index)) if R else float("nan"))
+
+
+# ---- cascade: lxmert prunes each query to its best `keep` pairs, the other three members score what is left (mms_score_ensemble_cascade) ----
+CASCADE_FLAG_NON_FINITE, CASCADE_FLAG_RESERVED_ID, CASCADE_FLAG_TOO_MANY = 1, 2, 4      # status[0] of mms_cascade_select (include/mmscore.h)
+
+
+def cascade_keep(query_id, stage1, keep: int, parts=None):
+    """The selection of the cascade on the host, the reference of ``mms_cascade_select``: within each query the rows are ordered by (``stage1``
+    descending, row ascending; -0.0 == +0.0, the fp32 values compared exactly) and the first ``min(keep, rows)`` are kept.
+    -> (kept bool [n], kept_list int32: the kept rows in ascending row order).  ``parts``: batch offsets (ascending row indices; 0 and n may be
+    left out) -- the device sees one batch per call, so a query cut by an offset is selected per part: never fewer rows kept, only more."""
+    import numpy as np
+    q = np.asarray(query_id).astype(np.int64).reshape(-1)
+    s = np.asarray(stage1, np.float32).astype(np.float64).reshape(-1) + 0.0          # + 0.0 folds -0.0 onto +0.0
+    n = len(q)
+    if len(s) != n:
+        raise ValueError("cascade_keep: %d query ids, %d scores" % (n, len(s)))
+    if keep < 1:
+        raise ValueError("cascade_keep: keep must be >= 1")
+    kept = np.zeros(n, bool)
+    cuts = sorted({0, n} | {int(c) for c in (parts if parts is not None else ()) if 0 < int(c) < n})
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        order = a + np.lexsort((np.arange(b - a), -s[a:b], q[a:b]))                  # by query, score descending, row ascending
+        qs = q[order]
+        start = np.flatnonzero(np.r_[True, qs[1:] != qs[:-1]])
+        rank = np.arange(b - a) - np.repeat(start, np.diff(np.r_[start, b - a]))
+        kept[order[rank < keep]] = True
+    return kept, np.flatnonzero(kept).astype(np.int32)
+
+
+def cascade_keep_device(query_id, stage1, keep: int, info: dict = None):
+    """``cascade_keep`` of ONE batch on the GPU (``mms_cascade_select``): -> (kept bool [n], kept_list int32 [n_kept]) as device tensors; one
+    synchronising read of the status word.  On a flag (a non-finite score, a query id equal to the reserved -1, more than 2^22 rows) the device
+    keeps every row; the result then comes from the host form.  ``info`` receives ``{"path", "flags", "n_kept", "queries", "largest_query"}``."""
+    import torch
+
+    from . import lib as _lib
+    from .ndcg import _check_rc, _ptr, _rows_on_device
+    (s, q), dev = _rows_on_device((stage1, query_id), ((torch.float32,), (torch.int64,)), "cascade_keep_device")
+    n = s.shape[0]
+    l = _lib.load()
+    ws_bytes = l.mms_cascade_workspace_bytes(n)
+    if ws_bytes < 0:
+        raise ValueError("cascade_keep_device: %d rows" % n)
+    ws = torch.empty((max(ws_bytes, 256),), dtype=torch.uint8, device=dev)
+    kept = torch.empty((n,), dtype=torch.uint8, device=dev)
+    kept_list = torch.empty((n,), dtype=torch.int32, device=dev)
+    status = torch.empty((4,), dtype=torch.int32, device=dev)
+    rc = l.mms_cascade_select(_ptr(q), _ptr(s), n, int(keep), _ptr(kept), _ptr(kept_list), status.data_ptr(), ws.data_ptr(), ws_bytes,
+                              torch.cuda.current_stream(dev).cuda_stream)
+    _check_rc(l, rc, "mms_cascade_select")
+    flags, n_kept, queries, largest = (int(v) for v in status.cpu().numpy())         # the one synchronising read
+    if info is not None:
+        info.update(path="host" if flags else "device", flags=flags, n_kept=n_kept, queries=queries, largest_query=largest)
+    if flags:
+        hk, hl = cascade_keep(q.cpu().numpy(), s.cpu().numpy(), keep)
+        return torch.from_numpy(hk).to(dev), torch.from_numpy(hl).to(dev)
+    return kept.bool(), kept_list[:n_kept]
+
+
+def cascade_members(members, kept):
+    """The member scores the cascade returns for the selection ``kept``: rows 0-2 of a pruned pair are 0.0, row 3 (lxmert, the first stage) stays.
+    ``members``: fp32 [4, n], numpy or a tensor (the result lives where ``members`` does)."""
+    import numpy as np
+    if hasattr(members, "detach"):
+        import torch
+        k = torch.as_tensor(kept, device=members.device).bool()
+        out = members.clone()
+        out[:3, ~k] = 0.0
+        return out
+    out = np.array(members, np.float32, copy=True)
+    out[:3, ~np.asarray(kept, bool)] = 0.0
+    return out
+
+
+def cascade_curve(query_id, product_id, members, rank_label, keeps, weights=WEIGHTS, gap=GAP, tie=TIE, k: int = 5, parts=None, where: str = "device"):
+    """What a given ``keep`` costs in nDCG, read off ONE full pass over the valid set (``members``: fp32 [4, n] of ``mms_score_ensemble``; member 3 is
+    the first stage).  -> a list with one dict per ``keep``:
+      ``keep``; ``kept``: the pairs the cascade would send through stage 2; ``fraction``: kept / n;
+      ``ndcg``: nDCG@k of the SUBMISSION rows of the cascade's scores -- ``fit_joint`` on ``cascade_members(members, kept)`` with the one-row weight
+      grid ``weights`` and the one-row filter grid ``(gap, tie)``, so that ``where="device"`` and ``where="host"`` give the same float;
+      ``changed``: the queries whose submission row differs from the full ensemble's (a row only one of the two writes counts), from
+      ``submission_rows`` on ``ndcg.merge_members`` of the host copies.
+    ``parts``: the batch offsets of the pass (``cascade_keep``).  The members of a pruned pair are exact zeros, as on the device; what the curve cannot
+    show is the round-off between a stage 2 of n_kept pairs and the full pass's launch regimes (<= 2e-5 on a score, include/mmscore.h)."""
+    import numpy as np
+
+    from . import ndcg
+    if where not in ("host", "device"):
+        raise ValueError("where must be 'host' or 'device', not %r" % (where,))
+    to_np = lambda x: x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+    q, p, mem = to_np(query_id).astype(np.int64), to_np(product_id).astype(np.int64), np.asarray(to_np(members), np.float32)
+    n = len(q)
+    grid = np.array([weights], np.float64)
+    filters = np.array([[gap, tie]], np.float64)
+    full_rows = submission_rows(q, p, ndcg.merge_members(mem, grid[0]), gap, tie)
+    out = []
+    for keep in keeps:
+        kept, _ = cascade_keep(q, mem[3], int(keep), parts)
+        cm = cascade_members(mem, kept)
+        if where == "device":
+            import torch
+            dev = members.device if hasattr(members, "detach") and members.is_cuda else torch.device("cuda", torch.cuda.current_device())
+            value = fit_joint(query_id, product_id, torch.from_numpy(cm).to(dev), rank_label, grid, filters, k, where="device")[2]
+        else:
+            value = fit_joint(q, p, cm, rank_label, grid, filters, k, where="host")[2]
+        rows = submission_rows(q, p, ndcg.merge_members(cm, grid[0]), gap, tie)
+        changed = sum(1 for qq in set(full_rows) | set(rows) if full_rows.get(qq) != rows.get(qq))
+        out.append(dict(keep=int(keep), kept=int(kept.sum()), fraction=float(kept.sum()) / n if n else 1.0, ndcg=float(value), changed=int(changed)))
+    return out

@@ -404,34 +404,48 @@ class EnsembleScorer:
         """The merge weights of the following passes (``scorers.EnsembleScorer.set_weights``), e.g. the winner of ``fit_weights_tsv_native``."""
         self.fused.set_weights(w)
 
-    def _score(self, zk_feed, s2f_feed, lx_feed):
-        merged, mem = self.fused(ensemble_feed(zk_feed, s2f_feed, lx_feed))
+    def _score(self, zk_feed, s2f_feed, lx_feed, cascade=None):
+        merged, mem = self.fused(ensemble_feed(zk_feed, s2f_feed, lx_feed), cascade=cascade)[:2]
         return merged.double().cpu().numpy(), tuple(m for m in mem.cpu().numpy())
 
-    def score_lines(self, tsv_lines, label_table, tok_tf, tok_hf, batch_pairs: int = 8192):
-        """tok_tf: WordPieceTokenizer as the TF sub-projects build it; tok_hf: the lxmert (HF) flavour."""
+    @staticmethod
+    def _cascade_info(info, kept, offsets):
+        if info is not None:
+            info.update(cascade_kept=int(kept), cascade_pairs=int(offsets[-1]), batch_offsets=[int(o) for o in offsets])
+
+    def score_lines(self, tsv_lines, label_table, tok_tf, tok_hf, batch_pairs: int = 8192, cascade_keep: int = None, info: dict = None):
+        """tok_tf: WordPieceTokenizer as the TF sub-projects build it; tok_hf: the lxmert (HF) flavour.
+        ``cascade_keep``: the cascade form of the fused call (``scorers.EnsembleScorer.score_prepared(cascade=)``) with each batch's query ids;
+        ``info`` then receives ``cascade_kept`` / ``cascade_pairs`` (pairs through stage 2 / all pairs) and ``batch_offsets``."""
         lines = [l for l in tsv_lines if l.strip() and "product_id" not in l]
         rec = [F.read_line(l, label_table, tok_tf) for l in lines]
         rec_s2f = [F.read_line(l, label_table, tok_tf, sen2forest=True) for l in lines]
         rec_hf = [F.read_line(l, label_table, tok_hf) for l in lines]
         merged, parts = [], [[], [], [], []]
+        kept_pairs = 0
         for s in range(0, len(rec), batch_pairs):
             zf = F.zk_batch(rec[s:s + batch_pairs], self.zk.cfg.text_len)
             lf = F.lxmert_batch(rec_hf[s:s + batch_pairs], self.lxmert.cfg.text_len)
             if not np.array_equal(zf["np_idx_class_labels"], lf["boxes_label_input_ids"]):
                 raise ValueError("the two tokenizer flavours disagree on a class name: the fused entry point takes one label-id tensor")
-            m, p4 = self._score(zf, F.zk_batch(rec_s2f[s:s + batch_pairs], self.zk.cfg.text_len), lf)
+            cascade = None if cascade_keep is None else (np.array([r.query_id for r in rec[s:s + batch_pairs]], np.int64), cascade_keep)
+            m, p4 = self._score(zf, F.zk_batch(rec_s2f[s:s + batch_pairs], self.zk.cfg.text_len), lf, cascade)
+            kept_pairs += self.fused.last_kept if cascade is not None else 0
             merged.append(m)
             for k in range(4):
                 parts[k].append(p4[k])
         cat = lambda xs, dt: np.concatenate(xs) if xs else np.zeros(0, dt)
         qid = np.array([r.query_id for r in rec], np.int64)
         pid = np.array([r.product_id for r in rec], np.int64)
+        if cascade_keep is not None:
+            self._cascade_info(info, kept_pairs, list(range(0, len(rec), batch_pairs)) + [len(rec)])
         return qid, pid, cat(merged, np.float64), tuple(cat(x, np.float32) for x in parts)
 
-    def _tsv_pass(self, tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members, relabel=None):
+    def _tsv_pass(self, tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members, relabel=None, cascade_keep=None, info=None):
         """The overlapped pass of the file-fed ensemble drivers with the outputs left on the device: -> (query_id, product_id, per batch: (merged,
-        member scores or None without ``members``)).  ``relabel``: see ``_answer_labels``."""
+        member scores or None without ``members``)).  ``relabel``: see ``_answer_labels``.  ``cascade_keep``: the batch's query ids go to the device
+        with the feed and the fused call runs in its cascade form (a query cut by a batch boundary is selected per part); ``info`` receives
+        ``cascade_kept`` / ``cascade_pairs`` and the pass's ``batch_offsets``."""
         if feat_decode not in ("host", "device"):
             raise ValueError("feat_decode must be 'host' or 'device', not %r" % (feat_decode,))
         # (kept between calls like stream_scores_tsv's; the fused feed reads the 2048-d features from the first pass only, the other two flavours skip their decode)
@@ -443,24 +457,37 @@ class EnsembleScorer:
                     feed = ensemble_feed(zf, nf_s2f.featurize_spans(*span, True), nf_lx.featurize_spans(*span))
                     q, pr = zf["query_id"].copy(), zf["product_id"].copy()
                     ids = {} if relabel is None else {"_query_id": q, "_product_id": pr}
+                    if cascade_keep is not None:
+                        ids["_query_id"] = q
                     yield q, pr, {**feed, **{k: zf[k] for k in FEAT_TEXT_KEYS if k in zf}, **ids}
 
             def score(d):
                 prep = self.fused.prepare(d if relabel is None else relabel(d))
-                return self.fused.score_prepared(prep) if members else self.fused.score_prepared(prep, False)
+                if cascade_keep is None:
+                    return self.fused.score_prepared(prep) if members else self.fused.score_prepared(prep, False)
+                res = self.fused.score_prepared(prep, members, cascade=(d["_query_id"], cascade_keep))
+                kept[0] += self.fused.last_kept
+                offsets.append(offsets[-1] + int(res[0].shape[0]))
+                return res[:2]
 
+            kept, offsets = [0], [0]
             qid, pid, out, _ = _overlapped_pass(batches(), self.zk.device, "feats", score)
+            if cascade_keep is not None:
+                self._cascade_info(info, kept[0], offsets)
         return qid, pid, out
 
     def evaluate_tsv_native(self, tsv_path, vocab_path, label_table, rank_label, k: int = 5, metric: str = "device", labels: str = "answer",
-                            batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host", info: dict = None, scores_out: dict = None):
+                            batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host", info: dict = None, scores_out: dict = None,
+                            cascade_keep: int = None):
         """A valid TSV file -> nDCG@k of the merged scores against the answer key (``pipeline.evaluate_tsv_native``, which see, for the ensemble):
         the pass of ``score_tsv_native`` with the merged scores left on the device, the zk members' label feed from the answer key
         (``labels="answer"``) or all ones (``labels="ones"``, today's feed), the metric on the GPU (``metric="device"``) or by
-        ``ndcg.ndcg_from_arrays`` on the fp64 copy of the scores (``metric="host"``) -- the same float."""
+        ``ndcg.ndcg_from_arrays`` on the fp64 copy of the scores (``metric="host"``) -- the same float.  ``cascade_keep``: the cascade form of
+        the fused call (``_tsv_pass``); ``info`` also receives ``cascade_kept`` / ``cascade_pairs`` / ``batch_offsets``."""
         _check_eval_args(metric, labels)
         rank_label, relabel = _relabel(labels, rank_label, self.zk.device)
-        qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=False, relabel=relabel)
+        qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=False, relabel=relabel,
+                                       cascade_keep=cascade_keep, info=info)
         score = torch.cat([m for m, _ in out]).double() if out else torch.zeros(0, dtype=torch.float64, device=self.zk.device)
         if scores_out is not None:
             scores_out.update(query_id=qid, product_id=pid, score=score)
@@ -536,32 +563,59 @@ class EnsembleScorer:
             scores_out.update(query_id=qid, product_id=pid, members=mem)
         return ensemble.fit_joint_resampled(qid, pid, mem, rank_label, grid, filters, k, info=info, **resample)
 
-    def score_tsv_native(self, tsv_path, vocab_path, label_table, batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host"):
+    def cascade_curve_tsv_native(self, tsv_path, vocab_path, label_table, rank_label, keeps, gap: float = None, tie: float = None, k: int = 5,
+                                 labels: str = "answer", batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host", where: str = "device",
+                                 scores_out: dict = None):
+        """A valid TSV file -> what each ``keep`` of ``keeps`` would cost: ONE full pass as ``fit_joint_tsv_native`` (the four member scores left on
+        the device), then ``ensemble.cascade_curve`` with the scorer's merge weights, the filter ``(gap, tie)`` (``None``: main.py's) and the pass's
+        batch offsets as ``parts`` -- per ``keep`` the kept fraction, the nDCG@k of the submission rows the cascade would produce and the queries
+        whose row changes.  Choose ``keep`` here, then pass it as ``cascade_keep`` to ``submission_tsv_native`` with the same ``batch_pairs``.
+        ``scores_out`` receives ``query_id`` / ``product_id`` (numpy), ``members`` (device fp32 [4, n]) and ``batch_offsets``."""
+        from . import ensemble
+        _check_eval_args("device", labels)
+        rank_label, relabel = _relabel(labels, rank_label, self.zk.device)
+        qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=True, relabel=relabel)
+        mem = torch.cat([m for _, m in out], 1) if out else torch.zeros((4, 0), dtype=torch.float32, device=self.zk.device)
+        offsets = np.cumsum([0] + [int(m.shape[0]) for m, _ in out]).tolist()
+        if scores_out is not None:
+            scores_out.update(query_id=qid, product_id=pid, members=mem, batch_offsets=offsets)
+        gap, tie = ensemble.GAP if gap is None else gap, ensemble.TIE if tie is None else tie
+        return ensemble.cascade_curve(qid, pid, mem, rank_label, keeps, self.weights, gap, tie, k, parts=offsets, where=where)
+
+    def score_tsv_native(self, tsv_path, vocab_path, label_table, batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host",
+                         cascade_keep: int = None, info: dict = None):
         """``score_lines`` on a TSV file through libmmfeat, decode and scoring overlapped: a producer thread decodes span batch i+1
         three times (zk flavour, zk with the sen2forest rewrite, lxmert flavour; ctypes releases the GIL, each featurizer rotates
         three pinned buffer sets) while the main thread copies batch i to the device and runs the ONE fused call on it.
         ``feat_decode="device"``: the zk-flavour pass gathers the features' base64 text and the GPU decodes it on the scoring stream in front of
-        the fused call (``stream_scores_tsv``); same scores, a bad record raises ValueError before the pass returns."""
-        qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=True)
+        the fused call (``stream_scores_tsv``); same scores, a bad record raises ValueError before the pass returns.
+        ``cascade_keep``: the cascade form of the fused call (``_tsv_pass``; members 0-2 of a pruned pair are zeros); ``info`` then receives
+        ``cascade_kept`` / ``cascade_pairs`` / ``batch_offsets``."""
+        qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=True, cascade_keep=cascade_keep,
+                                       info=info)
         if not out:
             return qid, pid, np.zeros(0, np.float64), tuple(np.zeros(0, np.float32) for _ in range(4))
         mem_all = torch.cat([mem for _, mem in out], 1).cpu().numpy()
         return qid, pid, torch.cat([m for m, _ in out]).double().cpu().numpy(), tuple(mem_all[k] for k in range(4))
 
     def submission_tsv_native(self, tsv_path, vocab_path, label_table, out_path=None, batch_pairs: int = 16384, threads: int = 0,
-                              feat_decode: str = "host", rank: str = "device", gap: float = None, tie: float = None):
+                              feat_decode: str = "host", rank: str = "device", gap: float = None, tie: float = None, cascade_keep: int = None,
+                              info: dict = None):
         """TSV file -> submission rows (``{query: [p1..p5]}``, optionally written to ``out_path``): the pass of ``score_tsv_native`` with the merged
         scores left on the device -- no member scores, no score read-back --, the ids uploaded once, and the uniqueness filter + top-5 on the GPU
         (``ensemble.submission_rows_device``; ``rank="host"``: ``ensemble.submission_rows`` on the fp64 copy of the scores, what a caller of
         ``score_tsv_native`` does).  Same rows either way.  ``gap`` / ``tie``: the filter's constants (``None``: ``ensemble.GAP`` / ``ensemble.TIE``,
-        main.py's), e.g. the winner of ``fit_filter_tsv_native``; both rank forms take them."""
+        main.py's), e.g. the winner of ``fit_filter_tsv_native``; both rank forms take them.  ``cascade_keep``: the cascade form of the fused call
+        (``_tsv_pass``) with the ``keep`` chosen on valid (``cascade_curve_tsv_native``); ``info`` then receives ``cascade_kept`` /
+        ``cascade_pairs`` / ``batch_offsets``."""
         from . import ensemble
         if feat_decode not in ("host", "device"):
             raise ValueError("feat_decode must be 'host' or 'device', not %r" % (feat_decode,))
         if rank not in ("host", "device"):
             raise ValueError("rank must be 'host' or 'device', not %r" % (rank,))
         gap, tie = ensemble.GAP if gap is None else gap, ensemble.TIE if tie is None else tie
-        qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=True)
+        qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=True, cascade_keep=cascade_keep,
+                                       info=info)
         out = [m for m, _ in out]
         if not out:
             rows = ensemble.submission_rows(qid, pid, np.zeros(0, np.float64), gap, tie)

@@ -369,11 +369,31 @@ class EnsembleScorer:
                                t["labels"].data_ptr(), t["lx"].data_ptr(), t["lxm"].data_ptr())
         return s, B, t
 
-    def score_prepared(self, prepared, members: bool = True):
-        """-> (merged [B], member scores [4,B] or None), device fp32."""
+    def score_prepared(self, prepared, members: bool = True, cascade=None):
+        """-> (merged [B], member scores [4,B] or None), device fp32.
+        ``cascade=(group_ids, keep)``: the cascade form (``mms_score_ensemble_cascade``, include/mmscore.h) -- lxmert scores every pair, the best
+        ``keep`` pairs of each query (``group_ids`` [B]: the query id of each pair) go through the other three members, a pruned pair's members
+        0-2 are exact zeros -- -> (merged, members, kept [B] bool); ``self.last_kept`` = the number of kept pairs."""
         s, B, keep = prepared
         merged = torch.empty((B,), device=self.device, dtype=torch.float32)
         mem = torch.empty((4, B), device=self.device, dtype=torch.float32) if members else None
+        if cascade is not None:
+            group_ids, n_keep = cascade
+            gid = self.zk._dev(group_ids, torch.int64)
+            if gid.shape != (B,):
+                raise ValueError("cascade: group_ids must hold one query id per pair")
+            kept = torch.empty((B,), device=self.device, dtype=torch.uint8)
+            nk = _lib.C.c_int64(0)
+            if B > 0:
+                st = torch.cuda.current_stream(self.device).cuda_stream
+                rc = self.lib.mms_score_ensemble_cascade(self.zk.handle._h, self.lds.handle._h, self.lxmert.handle._h, _lib.C.byref(s), gid.data_ptr(),
+                                                         int(n_keep), self.w, merged.data_ptr(), mem.data_ptr() if members else None,
+                                                         kept.data_ptr(), _lib.C.byref(nk), st)
+                if rc != 0:
+                    raise _lib.MmsError("mms_score_ensemble_cascade failed (%d): %s" % (rc, self.lib.mms_last_error(self.zk.handle._h).decode()))
+            self._keep = (keep, gid)
+            self.last_kept = int(nk.value)
+            return merged, mem, kept.bool()
         if B > 0:
             st = torch.cuda.current_stream(self.device).cuda_stream
             rc = self.lib.mms_score_ensemble(self.zk.handle._h, self.lds.handle._h, self.lxmert.handle._h, _lib.C.byref(s), self.w,
@@ -383,8 +403,8 @@ class EnsembleScorer:
         self._keep = keep
         return merged, mem
 
-    def __call__(self, feed: dict, members: bool = True):
-        return self.score_prepared(self.prepare(feed), members)
+    def __call__(self, feed: dict, members: bool = True, cascade=None):
+        return self.score_prepared(self.prepare(feed), members, cascade)
 
     def close(self):
         for m in (self.zk, self.lds, self.lxmert):
