@@ -1761,15 +1761,44 @@ int mms_version(void) { return MMS_ABI_VERSION; }
 const char* mms_global_error(void) { return g_err.c_str(); }
 const char* mms_last_error(const mms_handle* h) { return h ? h->err.c_str() : "null handle"; }
 
+namespace {
+// The checks and the tail of a handle-free entry point: the FIRST failing check wins (reject() after it changes nothing), the message carries
+// the function's name.  reject() evaluates its condition either way: a size that is only defined for arguments in range goes behind `!e.bad &&`.
+struct Entry {
+    const char* name;
+    const char* bad = nullptr;
+    void reject(bool failed, const char* msg) { if (!bad && failed) bad = msg; }
+    void one_score(const float* score_f32, const double* score_f64) {
+        reject((score_f32 != nullptr) == (score_f64 != nullptr), "exactly one of score_f32 / score_f64 must be given");
+    }
+    void value_out(const double* value_out, const double* bin_value, int64_t n_key_queries_total) {
+        reject(value_out && !bin_value, "value_out needs bin_value");
+        reject(value_out && n_key_queries_total < 1, "value_out needs n_key_queries_total >= 1");
+    }
+    void k_range(int32_t k, int32_t k_max, const char* msg) { reject(k < 1 || k > k_max, msg); }
+    void workspace(const void* ws, int64_t bytes, int64_t needed, const char* too_small) {
+        reject(!ws, "null pointer");
+        reject(reinterpret_cast<uintptr_t>(ws) & 255, "workspace must be 256-byte aligned");
+        reject(bytes < needed, too_small);
+    }
+    int fail() const { g_err = std::string(name) + ": " + bad; return MMS_ERR_ARG; }
+    // after the launches, which only enqueue: no allocation, no synchronisation, nothing read back
+    int done() const {
+        const hipError_t e = hipGetLastError();
+        if (e == hipSuccess) return 0;
+        g_err = std::string(name) + ": " + hipGetErrorString(e);
+        return MMS_ERR_HIP;
+    }
+};
+}  // namespace
+
 int mms_decode_feats_b64(const char* chars, const int64_t* char_off, const int32_t* rows, int64_t B, float* feats, int32_t* bad, void* stream) {
     if (B < 0 || B > INT32_MAX) { g_err = "mms_decode_feats_b64: B must be in [0, 2^31)"; return MMS_ERR_ARG; }
     if (B == 0) return 0;
     if (!chars || !char_off || !rows || !feats || !bad) { g_err = "mms_decode_feats_b64: null pointer"; return MMS_ERR_ARG; }
     if ((reinterpret_cast<uintptr_t>(chars) | reinterpret_cast<uintptr_t>(feats)) & 15) { g_err = "mms_decode_feats_b64: chars and feats must be 16-byte aligned"; return MMS_ERR_ARG; }
     launch_decode_feats_b64(chars, char_off, rows, B, feats, bad, (hipStream_t)stream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_err = std::string("mms_decode_feats_b64: ") + hipGetErrorString(e); return MMS_ERR_HIP; }
-    return 0;
+    return Entry{"mms_decode_feats_b64"}.done();
 }
 
 int64_t mms_rank_workspace_bytes(int64_t n) {
@@ -1779,21 +1808,18 @@ int64_t mms_rank_workspace_bytes(int64_t n) {
 int mms_rank_submission(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int64_t n, double gap,
                         double tie, void* workspace, int64_t workspace_bytes, int64_t max_queries, int64_t* out_query, int64_t* out_products,
                         int32_t* out_count, int32_t* status, void* stream) {
-    if (n < 0 || n > MMS_RANK_MAX_ROWS) { g_err = "mms_rank_submission: n must be in [0, MMS_RANK_MAX_ROWS]"; return MMS_ERR_ARG; }
-    if (max_queries < 0) { g_err = "mms_rank_submission: max_queries must be >= 0"; return MMS_ERR_ARG; }
-    if ((score_f32 != nullptr) == (score_f64 != nullptr)) { g_err = "mms_rank_submission: exactly one of score_f32 / score_f64 must be given"; return MMS_ERR_ARG; }
-    if (!status) { g_err = "mms_rank_submission: null status"; return MMS_ERR_ARG; }
-    if (n > 0) {
-        if (!query_id || !product_id || !workspace || !out_query || !out_products || !out_count) { g_err = "mms_rank_submission: null pointer"; return MMS_ERR_ARG; }
-        if (reinterpret_cast<uintptr_t>(workspace) & 255) { g_err = "mms_rank_submission: workspace must be 256-byte aligned"; return MMS_ERR_ARG; }
-        if (workspace_bytes < (int64_t)rank_workspace_bytes(n)) { g_err = "mms_rank_submission: workspace smaller than mms_rank_workspace_bytes(n)"; return MMS_ERR_ARG; }
-    }
-    // (only enqueues: three fills and eight kernels; no allocation, no synchronisation, nothing read back)
+    Entry e{"mms_rank_submission"};
+    e.reject(n < 0 || n > MMS_RANK_MAX_ROWS, "n must be in [0, MMS_RANK_MAX_ROWS]");
+    e.reject(max_queries < 0, "max_queries must be >= 0");
+    e.one_score(score_f32, score_f64);
+    e.reject(!status, "null status");
+    e.reject(n > 0 && (!query_id || !product_id || !out_query || !out_products || !out_count), "null pointer");
+    if (!e.bad && n > 0) e.workspace(workspace, workspace_bytes, (int64_t)rank_workspace_bytes(n), "workspace smaller than mms_rank_workspace_bytes(n)");
+    if (e.bad) return e.fail();
+    // (three fills and eight kernels)
     launch_rank_submission(query_id, product_id, score_f32, score_f64, (int)n, gap, tie, workspace, (int)std::min<int64_t>(max_queries, INT32_MAX), out_query,
                            out_products, out_count, status, (hipStream_t)stream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_err = std::string("mms_rank_submission: ") + hipGetErrorString(e); return MMS_ERR_HIP; }
-    return 0;
+    return e.done();
 }
 
 int64_t mms_ndcg_workspace_bytes(int64_t n, int64_t n_key_queries, int64_t n_key_products) {
@@ -1813,44 +1839,37 @@ const char* ndcg_args(const int64_t* query_id, const int64_t* product_id, int64_
     if (n > 0 && (!query_id || !product_id)) return "null pointer";
     if (Qa > 0 && (!key_query || !key_off)) return "null pointer";
     if (Tk > 0 && (!key_product || Qa == 0)) return Qa == 0 ? "key products without key queries" : "null pointer";
-    if (Qa > 0) {
-        if (!workspace) return "null pointer";
-        if (reinterpret_cast<uintptr_t>(workspace) & 255) return "workspace must be 256-byte aligned";
-        if (workspace_bytes < (int64_t)ndcg_workspace_bytes(n, Qa, Tk)) return "workspace smaller than mms_ndcg_workspace_bytes(n, n_key_queries, n_key_products)";
-    }
-    return nullptr;
+    Entry e{nullptr};
+    if (Qa > 0) e.workspace(workspace, workspace_bytes, (int64_t)ndcg_workspace_bytes(n, Qa, Tk), "workspace smaller than mms_ndcg_workspace_bytes(n, n_key_queries, n_key_products)");
+    return e.bad;
 }
 }  // namespace
 
 int mms_key_relevance(const int64_t* query_id, const int64_t* product_id, int64_t n, const int64_t* key_query, const int64_t* key_off,
                       const int64_t* key_product, int64_t n_key_queries, int64_t n_key_products, void* workspace, int64_t workspace_bytes,
                       int64_t* labels_out, int32_t* status, void* stream) {
-    const char* bad = ndcg_args(query_id, product_id, n, key_query, key_off, key_product, n_key_queries, n_key_products, workspace, workspace_bytes, status);
-    if (!bad && n > 0 && !labels_out) bad = "null pointer";
-    if (bad) { g_err = std::string("mms_key_relevance: ") + bad; return MMS_ERR_ARG; }
-    // (only enqueues: fills and five kernels; no allocation, no synchronisation, nothing read back)
+    Entry e{"mms_key_relevance", ndcg_args(query_id, product_id, n, key_query, key_off, key_product, n_key_queries, n_key_products, workspace, workspace_bytes, status)};
+    e.reject(n > 0 && !labels_out, "null pointer");
+    if (e.bad) return e.fail();
+    // (fills and five kernels)
     launch_ndcg(query_id, product_id, nullptr, nullptr, (int)n, key_query, key_off, key_product, (int)n_key_queries, (int)n_key_products, 1, 1, workspace,
                 labels_out, nullptr, nullptr, nullptr, status, (hipStream_t)stream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_err = std::string("mms_key_relevance: ") + hipGetErrorString(e); return MMS_ERR_HIP; }
-    return 0;
+    return e.done();
 }
 
 int mms_ndcg_at_k(const int64_t* query_id, const int64_t* product_id, const float* score_f32, const double* score_f64, int64_t n,
                   const int64_t* key_query, const int64_t* key_off, const int64_t* key_product, int64_t n_key_queries, int64_t n_key_products, int32_t k,
                   int32_t allow_missing, void* workspace, int64_t workspace_bytes, int32_t* out_code, int64_t* out_topk, int64_t* hist, int32_t* status,
                   void* stream) {
-    const char* bad = ndcg_args(query_id, product_id, n, key_query, key_off, key_product, n_key_queries, n_key_products, workspace, workspace_bytes, status);
-    if (!bad && (k < 1 || k > MMS_NDCG_MAX_K)) bad = "k must be in [1, MMS_NDCG_MAX_K]";
-    if (!bad && (score_f32 != nullptr) == (score_f64 != nullptr)) bad = "exactly one of score_f32 / score_f64 must be given";
-    if (!bad && (!hist || (n_key_queries > 0 && !out_code))) bad = "null pointer";
-    if (bad) { g_err = std::string("mms_ndcg_at_k: ") + bad; return MMS_ERR_ARG; }
-    // (only enqueues: four fills and eight kernels; no allocation, no synchronisation, nothing read back)
+    Entry e{"mms_ndcg_at_k", ndcg_args(query_id, product_id, n, key_query, key_off, key_product, n_key_queries, n_key_products, workspace, workspace_bytes, status)};
+    e.k_range(k, MMS_NDCG_MAX_K, "k must be in [1, MMS_NDCG_MAX_K]");
+    e.one_score(score_f32, score_f64);
+    e.reject(!hist || (n_key_queries > 0 && !out_code), "null pointer");
+    if (e.bad) return e.fail();
+    // (four fills and eight kernels)
     launch_ndcg(query_id, product_id, score_f32, score_f64, (int)n, key_query, key_off, key_product, (int)n_key_queries, (int)n_key_products, k,
                 allow_missing != 0, workspace, nullptr, out_code, out_topk, hist, status, (hipStream_t)stream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_err = std::string("mms_ndcg_at_k: ") + hipGetErrorString(e); return MMS_ERR_HIP; }
-    return 0;
+    return e.done();
 }
 
 int64_t mms_ndcg_sweep_workspace_bytes(int64_t n, int64_t n_key_queries, int64_t n_key_products, int32_t n_members) {
@@ -1863,23 +1882,20 @@ int mms_ndcg_weight_sweep(const int64_t* query_id, const int64_t* product_id, co
                           const double* weights, int64_t n_weights, int32_t k, int32_t allow_missing, const double* bin_value, int64_t n_key_queries_total,
                           void* workspace, int64_t workspace_bytes, int64_t* hist_out, double* value_out, int32_t* status, void* stream) {
     // (the shared checks with a workspace of 0 bytes required: the sweep's own size is checked below)
-    const char* bad = ndcg_args(query_id, product_id, n, key_query, key_off, key_product, n_key_queries, n_key_products, workspace, INT64_MAX, status);
-    if (!bad && (n_members < 1 || n_members > MMS_SWEEP_MAX_MEMBERS)) bad = "n_members must be in [1, MMS_SWEEP_MAX_MEMBERS]";
-    if (!bad && (n_weights < 0 || n_weights > MMS_SWEEP_MAX_WEIGHTS)) bad = "n_weights must be in [0, MMS_SWEEP_MAX_WEIGHTS]";
-    if (!bad && (k < 1 || k > MMS_NDCG_MAX_K)) bad = "k must be in [1, MMS_NDCG_MAX_K]";
-    if (!bad && n > 0 && !members) bad = "null pointer";
-    if (!bad && n_weights > 0 && (!weights || !hist_out)) bad = "null pointer";
-    if (!bad && value_out && !bin_value) bad = "value_out needs bin_value";
-    if (!bad && value_out && n_key_queries_total < 1) bad = "value_out needs n_key_queries_total >= 1";
-    if (!bad && n_key_queries > 0 && workspace_bytes < (int64_t)ndcg_sweep_workspace_bytes(n, n_key_queries, n_key_products, n_members))
-        bad = "workspace smaller than mms_ndcg_sweep_workspace_bytes(n, n_key_queries, n_key_products, n_members)";
-    if (bad) { g_err = std::string("mms_ndcg_weight_sweep: ") + bad; return MMS_ERR_ARG; }
-    // (only enqueues: fills and at most ten kernels; no allocation, no synchronisation, nothing read back)
+    Entry e{"mms_ndcg_weight_sweep", ndcg_args(query_id, product_id, n, key_query, key_off, key_product, n_key_queries, n_key_products, workspace, INT64_MAX, status)};
+    e.reject(n_members < 1 || n_members > MMS_SWEEP_MAX_MEMBERS, "n_members must be in [1, MMS_SWEEP_MAX_MEMBERS]");
+    e.reject(n_weights < 0 || n_weights > MMS_SWEEP_MAX_WEIGHTS, "n_weights must be in [0, MMS_SWEEP_MAX_WEIGHTS]");
+    e.k_range(k, MMS_NDCG_MAX_K, "k must be in [1, MMS_NDCG_MAX_K]");
+    e.reject(n > 0 && !members, "null pointer");
+    e.reject(n_weights > 0 && (!weights || !hist_out), "null pointer");
+    e.value_out(value_out, bin_value, n_key_queries_total);
+    e.reject(!e.bad && n_key_queries > 0 && workspace_bytes < (int64_t)ndcg_sweep_workspace_bytes(n, n_key_queries, n_key_products, n_members),
+             "workspace smaller than mms_ndcg_sweep_workspace_bytes(n, n_key_queries, n_key_products, n_members)");
+    if (e.bad) return e.fail();
+    // (fills and at most ten kernels)
     launch_ndcg_sweep(query_id, product_id, members, n_members, (int)n, key_query, key_off, key_product, (int)n_key_queries, (int)n_key_products, weights,
                       n_weights, k, allow_missing != 0, bin_value, n_key_queries_total, workspace, hist_out, value_out, status, (hipStream_t)stream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_err = std::string("mms_ndcg_weight_sweep: ") + hipGetErrorString(e); return MMS_ERR_HIP; }
-    return 0;
+    return e.done();
 }
 
 int64_t mms_filter_sweep_workspace_bytes(int64_t n, int64_t n_key_queries, int64_t n_key_products) {
@@ -1892,22 +1908,19 @@ int mms_filter_sweep(const int64_t* query_id, const int64_t* product_id, const f
                      const double* filters, int64_t n_filters, int32_t k, int32_t allow_missing, const double* bin_value, int64_t n_key_queries_total,
                      void* workspace, int64_t workspace_bytes, int64_t* hist_out, double* value_out, int32_t* code_out, int32_t* status, void* stream) {
     // (the shared checks with a workspace of 0 bytes required: the sweep's own size is checked below)
-    const char* bad = ndcg_args(query_id, product_id, n, key_query, key_off, key_product, n_key_queries, n_key_products, workspace, INT64_MAX, status);
-    if (!bad && (n_filters < 0 || n_filters > MMS_FILTER_MAX)) bad = "n_filters must be in [0, MMS_FILTER_MAX]";
-    if (!bad && (k < 1 || k > MMS_FILTER_MAX_K)) bad = "k must be in [1, MMS_FILTER_MAX_K]";
-    if (!bad && (score_f32 != nullptr) == (score_f64 != nullptr)) bad = "exactly one of score_f32 / score_f64 must be given";
-    if (!bad && n_filters > 0 && (!filters || !hist_out)) bad = "null pointer";
-    if (!bad && value_out && !bin_value) bad = "value_out needs bin_value";
-    if (!bad && value_out && n_key_queries_total < 1) bad = "value_out needs n_key_queries_total >= 1";
-    if (!bad && n_key_queries > 0 && workspace_bytes < (int64_t)filter_sweep_workspace_bytes(n, n_key_queries, n_key_products))
-        bad = "workspace smaller than mms_filter_sweep_workspace_bytes(n, n_key_queries, n_key_products)";
-    if (bad) { g_err = std::string("mms_filter_sweep: ") + bad; return MMS_ERR_ARG; }
-    // (only enqueues: fills and at most fifteen kernels; no allocation, no synchronisation, nothing read back)
+    Entry e{"mms_filter_sweep", ndcg_args(query_id, product_id, n, key_query, key_off, key_product, n_key_queries, n_key_products, workspace, INT64_MAX, status)};
+    e.reject(n_filters < 0 || n_filters > MMS_FILTER_MAX, "n_filters must be in [0, MMS_FILTER_MAX]");
+    e.k_range(k, MMS_FILTER_MAX_K, "k must be in [1, MMS_FILTER_MAX_K]");
+    e.one_score(score_f32, score_f64);
+    e.reject(n_filters > 0 && (!filters || !hist_out), "null pointer");
+    e.value_out(value_out, bin_value, n_key_queries_total);
+    e.reject(!e.bad && n_key_queries > 0 && workspace_bytes < (int64_t)filter_sweep_workspace_bytes(n, n_key_queries, n_key_products),
+             "workspace smaller than mms_filter_sweep_workspace_bytes(n, n_key_queries, n_key_products)");
+    if (e.bad) return e.fail();
+    // (fills and at most fifteen kernels)
     launch_filter_sweep(query_id, product_id, score_f32, score_f64, (int)n, key_query, key_off, key_product, (int)n_key_queries, (int)n_key_products, filters,
                         n_filters, k, allow_missing != 0, bin_value, n_key_queries_total, workspace, hist_out, value_out, code_out, status, (hipStream_t)stream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_err = std::string("mms_filter_sweep: ") + hipGetErrorString(e); return MMS_ERR_HIP; }
-    return 0;
+    return e.done();
 }
 
 int64_t mms_joint_sweep_workspace_bytes(int64_t n, int64_t n_key_queries, int64_t n_key_products, int32_t n_members, int64_t tiles_per_chunk) {
@@ -1924,29 +1937,26 @@ int joint_sweep_entry(const char* name, const int64_t* query_id, const int64_t* 
                       const double* bin_value, int64_t n_key_queries_total, void* workspace, int64_t workspace_bytes, int64_t* hist_out, double* value_out,
                       uint8_t* code_out, int64_t code_bytes, int32_t* status, void* stream) {
     // (the shared checks with a workspace of 0 bytes required: the sweep's own size is checked below)
-    const char* bad = ndcg_args(query_id, product_id, n, key_query, key_off, key_product, n_key_queries, n_key_products, workspace, INT64_MAX, status);
-    if (!bad && (n_members < 1 || n_members > MMS_SWEEP_MAX_MEMBERS)) bad = "n_members must be in [1, MMS_SWEEP_MAX_MEMBERS]";
-    if (!bad && (n_weights < 0 || n_weights > MMS_JOINT_MAX_ITEMS)) bad = "n_weights must be in [0, MMS_JOINT_MAX_ITEMS]";
-    if (!bad && (n_filters < 0 || n_filters > MMS_FILTER_MAX)) bad = "n_filters must be in [0, MMS_FILTER_MAX]";
-    if (!bad && n_weights * n_filters > MMS_JOINT_MAX_ITEMS) bad = "n_weights * n_filters must be at most MMS_JOINT_MAX_ITEMS";
-    if (!bad && (k < 1 || k > MMS_FILTER_MAX_K)) bad = "k must be in [1, MMS_FILTER_MAX_K]";
-    if (!bad && n > 0 && !members) bad = "null pointer";
-    if (!bad && ((n_weights > 0 && !weights) || (n_filters > 0 && !filters))) bad = "null pointer";
-    if (!bad && value_out && !bin_value) bad = "value_out needs bin_value";
-    if (!bad && value_out && n_key_queries_total < 1) bad = "value_out needs n_key_queries_total >= 1";
-    if (!bad && n_key_queries > 0 &&
-        joint_sweep_chunk_tiles(n, n_key_queries, n_key_products, n_members, n_weights, n_filters, k, hist_out != nullptr, workspace_bytes) < 1)
-        bad = "workspace smaller than mms_joint_sweep_workspace_bytes(n, n_key_queries, n_key_products, n_members, 1) (plus one tile's histograms without hist_out)";
-    if (!bad && code_bytes != (code_out ? n_filters * n_key_queries * ((n_weights + 63) / 64 * 64) : 0))
-        bad = code_out ? "code_bytes must be n_filters * n_key_queries * Wp, Wp = n_weights rounded up to a multiple of 64" : "code_bytes without code_out";
-    if (bad) { g_err = std::string(name) + ": " + bad; return MMS_ERR_ARG; }
-    // (only enqueues: fills and kernels; no allocation, no synchronisation, nothing read back)
+    Entry e{name, ndcg_args(query_id, product_id, n, key_query, key_off, key_product, n_key_queries, n_key_products, workspace, INT64_MAX, status)};
+    e.reject(n_members < 1 || n_members > MMS_SWEEP_MAX_MEMBERS, "n_members must be in [1, MMS_SWEEP_MAX_MEMBERS]");
+    e.reject(n_weights < 0 || n_weights > MMS_JOINT_MAX_ITEMS, "n_weights must be in [0, MMS_JOINT_MAX_ITEMS]");
+    e.reject(n_filters < 0 || n_filters > MMS_FILTER_MAX, "n_filters must be in [0, MMS_FILTER_MAX]");
+    e.reject(!e.bad && n_weights * n_filters > MMS_JOINT_MAX_ITEMS, "n_weights * n_filters must be at most MMS_JOINT_MAX_ITEMS");
+    e.k_range(k, MMS_FILTER_MAX_K, "k must be in [1, MMS_FILTER_MAX_K]");
+    e.reject(n > 0 && !members, "null pointer");
+    e.reject((n_weights > 0 && !weights) || (n_filters > 0 && !filters), "null pointer");
+    e.value_out(value_out, bin_value, n_key_queries_total);
+    e.reject(!e.bad && n_key_queries > 0 &&
+                 joint_sweep_chunk_tiles(n, n_key_queries, n_key_products, n_members, n_weights, n_filters, k, hist_out != nullptr, workspace_bytes) < 1,
+             "workspace smaller than mms_joint_sweep_workspace_bytes(n, n_key_queries, n_key_products, n_members, 1) (plus one tile's histograms without hist_out)");
+    e.reject(!e.bad && code_bytes != (code_out ? n_filters * n_key_queries * ((n_weights + 63) / 64 * 64) : 0),
+             code_out ? "code_bytes must be n_filters * n_key_queries * Wp, Wp = n_weights rounded up to a multiple of 64" : "code_bytes without code_out");
+    if (e.bad) return e.fail();
+    // (fills and kernels)
     launch_joint_sweep(query_id, product_id, members, n_members, (int)n, key_query, key_off, key_product, (int)n_key_queries, (int)n_key_products, weights,
                        n_weights, filters, n_filters, k, allow_missing != 0, bin_value, n_key_queries_total, workspace, workspace_bytes, hist_out, value_out,
                        code_out, status, (hipStream_t)stream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_err = std::string(name) + ": " + hipGetErrorString(e); return MMS_ERR_HIP; }
-    return 0;
+    return e.done();
 }
 }  // namespace
 
@@ -1990,25 +2000,23 @@ int mms_resample_select(const uint8_t* code, int64_t code_bytes, int64_t n_weigh
                         const uint8_t* count_eval, int64_t n_replicates, const double* byte_value, const int64_t* probe_item, int64_t n_probes,
                         void* workspace, int64_t workspace_bytes, int64_t* best, double* fit_value, double* eval_value, double* probe_fit,
                         double* probe_eval, int32_t* status, void* stream) {
-    const char* bad = resample_counts(n_weights, n_filters, n_key_queries, n_replicates);
-    if (!bad && (n_probes < 0 || n_probes > MMS_RESAMPLE_MAX_PROBES)) bad = "n_probes must be in [0, MMS_RESAMPLE_MAX_PROBES]";
-    if (!bad && !status) bad = "null status";
-    if (!bad && code_bytes != n_filters * n_key_queries * ((n_weights + 63) / 64 * 64))
-        bad = "code_bytes must be n_filters * n_key_queries * Wp, Wp = n_weights rounded up to a multiple of 64";
-    if (!bad && code_bytes > 0 && !code) bad = "null pointer";
-    if (!bad && n_replicates > 0 && (!byte_value || !best || !fit_value || !eval_value || !workspace)) bad = "null pointer";
-    if (!bad && n_replicates > 0 && n_key_queries > 0 && (!count_fit || !count_eval)) bad = "null pointer";
-    if (!bad && n_probes > 0 && (!probe_item || (n_replicates > 0 && (!probe_fit || !probe_eval)))) bad = "null pointer";
-    if (!bad && n_replicates > 0 && (reinterpret_cast<uintptr_t>(workspace) & 255)) bad = "workspace must be 256-byte aligned";
-    if (!bad && n_replicates > 0 && workspace_bytes < (int64_t)resample_workspace_bytes(n_weights, n_filters, n_key_queries, n_replicates))
-        bad = "workspace smaller than mms_resample_workspace_bytes(n_weights, n_filters, n_key_queries, n_replicates)";
-    if (bad) { g_err = std::string("mms_resample_select: ") + bad; return MMS_ERR_ARG; }
-    // (only enqueues: four kernels; no allocation, no synchronisation, nothing read back)
+    Entry e{"mms_resample_select", resample_counts(n_weights, n_filters, n_key_queries, n_replicates)};
+    e.reject(n_probes < 0 || n_probes > MMS_RESAMPLE_MAX_PROBES, "n_probes must be in [0, MMS_RESAMPLE_MAX_PROBES]");
+    e.reject(!status, "null status");
+    e.reject(!e.bad && code_bytes != n_filters * n_key_queries * ((n_weights + 63) / 64 * 64),
+             "code_bytes must be n_filters * n_key_queries * Wp, Wp = n_weights rounded up to a multiple of 64");
+    e.reject(code_bytes > 0 && !code, "null pointer");
+    e.reject(n_replicates > 0 && (!byte_value || !best || !fit_value || !eval_value), "null pointer");
+    e.reject(n_replicates > 0 && n_key_queries > 0 && (!count_fit || !count_eval), "null pointer");
+    e.reject(n_probes > 0 && (!probe_item || (n_replicates > 0 && (!probe_fit || !probe_eval))), "null pointer");
+    if (!e.bad && n_replicates > 0)
+        e.workspace(workspace, workspace_bytes, (int64_t)resample_workspace_bytes(n_weights, n_filters, n_key_queries, n_replicates),
+                    "workspace smaller than mms_resample_workspace_bytes(n_weights, n_filters, n_key_queries, n_replicates)");
+    if (e.bad) return e.fail();
+    // (four kernels)
     launch_resample_select(code, n_weights, n_filters, (int)n_key_queries, count_fit, count_eval, (int)n_replicates, byte_value, probe_item, (int)n_probes,
                            workspace, best, fit_value, eval_value, probe_fit, probe_eval, status, (hipStream_t)stream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_err = std::string("mms_resample_select: ") + hipGetErrorString(e); return MMS_ERR_HIP; }
-    return 0;
+    return e.done();
 }
 
 int mms_create(const mms_config* cfg, mms_handle** out) {
@@ -2431,19 +2439,16 @@ int64_t mms_cascade_workspace_bytes(int64_t n) {
 
 int mms_cascade_select(const int64_t* group_ids, const float* score_f32, int64_t n, int32_t keep, uint8_t* kept_u8, int32_t* kept_list_i32, int32_t* status,
                        void* workspace, int64_t workspace_bytes, void* stream) {
-    if (n < 0 || n > INT32_MAX) { g_err = "mms_cascade_select: n must be in [0, 2^31)"; return MMS_ERR_ARG; }
-    if (keep < 1) { g_err = "mms_cascade_select: keep must be >= 1"; return MMS_ERR_ARG; }
-    if (!status) { g_err = "mms_cascade_select: null status"; return MMS_ERR_ARG; }
-    if (n > 0) {
-        if (!group_ids || !score_f32 || !kept_u8 || !kept_list_i32 || !workspace) { g_err = "mms_cascade_select: null pointer"; return MMS_ERR_ARG; }
-        if (reinterpret_cast<uintptr_t>(workspace) & 255) { g_err = "mms_cascade_select: workspace must be 256-byte aligned"; return MMS_ERR_ARG; }
-        if (workspace_bytes < (int64_t)cascade_workspace_bytes(n)) { g_err = "mms_cascade_select: workspace smaller than mms_cascade_workspace_bytes(n)"; return MMS_ERR_ARG; }
-    }
-    // (only enqueues: three fills and nine kernels; no allocation, no synchronisation, nothing read back)
+    Entry e{"mms_cascade_select"};
+    e.reject(n < 0 || n > INT32_MAX, "n must be in [0, 2^31)");
+    e.reject(keep < 1, "keep must be >= 1");
+    e.reject(!status, "null status");
+    e.reject(n > 0 && (!group_ids || !score_f32 || !kept_u8 || !kept_list_i32), "null pointer");
+    if (!e.bad && n > 0) e.workspace(workspace, workspace_bytes, (int64_t)cascade_workspace_bytes(n), "workspace smaller than mms_cascade_workspace_bytes(n)");
+    if (e.bad) return e.fail();
+    // (three fills and nine kernels)
     launch_cascade_select(group_ids, score_f32, n, keep, kept_u8, kept_list_i32, status, workspace, (hipStream_t)stream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) { g_err = std::string("mms_cascade_select: ") + hipGetErrorString(e); return MMS_ERR_HIP; }
-    return 0;
+    return e.done();
 }
 
 // buffers of the cascade that scale with the call (B pairs) and with the second stage (n_kept pairs): both grow on demand and are kept

@@ -50,8 +50,7 @@ FilterWs filter_layout(void* base, long long n, long long Qa, long long Tk) {
 __global__ __launch_bounds__(256) void k_filter_pack(int n, NdcgLists L, RankStats S, const int* __restrict__ rstatus, int* status, FilterRec* __restrict__ rec) {
     const int x = blockIdx.x * 256 + threadIdx.x;
     if (x == 0) {                                                            // flags of the product statistics: every row counts, listed or not
-        const int f = rstatus[2];
-        const int t = (f & 2) | (f & 8) | ((f & 1) << 4);
+        const int t = sweep_flags_of_rank(rstatus[2]);
         if (t) atomicOr(&status[2], t);
     }
     if (x >= n || x >= status[1]) return;
@@ -175,12 +174,10 @@ void launch_filter_sweep(const int64_t* query_id, const int64_t* product_id, con
                 const int sel_blocks = (int)std::min<long long>(2048, ((long long)Qa + 3) / 4);
                 hipLaunchKernelGGL(k_filter_unfiltered, dim3(sel_blocks), dim3(256), 0, st, Qa, k, L, (const FilterRec*)f.rec, f.umask);
                 const SweepGrid sg = sweep_grid(G, Qa);
-#define FSWEEP_CASE(K) case K: hipLaunchKernelGGL((k_filter_sweep<K>), dim3(sg.grid), dim3(256), 0, st, filters, G, Qa, sg.slabs, sg.tasks, L, (const FilterRec*)f.rec, (const int*)f.umask, (u64*)hist_out, code_out); break
-                switch (k) {
-                    FSWEEP_CASE(1); FSWEEP_CASE(2); FSWEEP_CASE(3); FSWEEP_CASE(4);
-                    default: FSWEEP_CASE(5);
-                }
-#undef FSWEEP_CASE
+                with_k<MMS_FILTER_MAX_K>(k, [&](auto kc) {
+                    hipLaunchKernelGGL((k_filter_sweep<decltype(kc)::value>), dim3(sg.grid), dim3(256), 0, st, filters, G, Qa, sg.slabs, sg.tasks, L,
+                                       (const FilterRec*)f.rec, (const int*)f.umask, (u64*)hist_out, code_out);
+                });
             }
         }
     }

@@ -30,6 +30,7 @@
 // Integer atomics only, and the order inside a list cannot matter because the selection key (score with -0.0 == +0.0, row) is total and best / rows at best /
 // rest are order-free: equal inputs give equal bytes, whatever the chunk size.  No kernel waits on another workgroup.
 #include "rank_tables.h"
+#include "merge_members.h"
 
 #pragma clang fp contract(off)
 
@@ -48,8 +49,6 @@ struct __attribute__((aligned(16))) BestD { double best; double d; };
 
 static_assert(sizeof(MemRec<4>) == 16 && sizeof(MemRec<8>) == 32 && sizeof(JointRec<4>) == 32 && sizeof(JointRec<8>) == 64 && sizeof(BestD) == 16, "joint_layout sizes the records");
 
-inline int joint_mp(int M) { return M <= 4 ? 4 : 8; }
-
 struct JointWs {
     char* rank; int* rstatus;
     int* pfill;                                             // [cap] 0
@@ -66,7 +65,7 @@ struct JointWs {
 JointWs joint_layout(void* base, long long n, long long Qa, long long Tk, int M) {
     JointWs j{};
     j.cap = rank_table_slots(n);
-    const size_t c = (size_t)j.cap, r = (size_t)(n > 0 ? n : 1), mp = (size_t)joint_mp(M);
+    const size_t c = (size_t)j.cap, r = (size_t)(n > 0 ? n : 1), mp = (size_t)member_mp(M);
     Carver cv{(char*)base, up256((size_t)ndcg_workspace_bytes(n, Qa, Tk))};
     cv.take(j.rank, (size_t)rank_workspace_bytes(n));
     cv.take(j.rstatus, 4);
@@ -132,8 +131,7 @@ __global__ __launch_bounds__(256) void k_joint_pack_p(const float* __restrict__ 
     if (x >= n || x >= hdr[0]) return;
     const int r = plist[x];                                                  // inside [0, n): k_joint_scatter wrote it
     MemRec<MP> o;
-#pragma unroll
-    for (int m = 0; m < MP; ++m) o.s[m] = m < M ? members[(size_t)m * n + r] : 0.0f;
+    load_members<MP>(members, M, n, r, o.s);
     prec[x] = o;
 }
 
@@ -143,41 +141,20 @@ __global__ __launch_bounds__(256) void k_joint_pack_q(const float* __restrict__ 
                                                       const int* __restrict__ pdense, const int* __restrict__ rstatus, int* status, JointRec<MP>* __restrict__ qrec) {
     const int x = blockIdx.x * 256 + threadIdx.x;
     if (x == 0) {                                                            // flags of the product statistics: every row counts, listed or not
-        const int f = rstatus[2];
-        const int t = (f & 2) | (f & 8) | ((f & 1) << 4);
+        const int t = sweep_flags_of_rank(rstatus[2]);
         if (t) atomicOr(&status[2], t);
     }
     if (x >= n || x >= status[1]) return;
     const int r = L.list[x];                                                 // inside [0, n): k_scatter wrote it
     const int ps = pslot[r];
     JointRec<MP> o{};
-#pragma unroll
-    for (int m = 0; m < MP; ++m) o.s[m] = m < M ? members[(size_t)m * n + r] : 0.0f;
+    load_members<MP>(members, M, n, r, o.s);
     o.meta = ((unsigned)r << 1) | (unsigned)L.rel[r];                       // r < 2^22
     o.prod = ps >= 0 ? pdense[ps] : -1;
     qrec[x] = o;
 }
 
 // ---- per chunk of weight tiles ----
-
-// The merge of the contract over the MP padded members.  A padded member (m >= M) has score 0 and weight 0: its term adds +0.0, which can change the
-// sign of a zero sum and nothing else -- and -0.0 compares, ranks and subtracts as +0.0.  ONE statement sequence for the statistics and the sweep.
-template <int MP>
-__device__ __forceinline__ double merged(const double (&w)[MP], const float (&m)[MP]) {
-    double s = w[0] * (double)m[0];
-#pragma unroll
-    for (int i = 1; i < MP; ++i) {
-        const double prod = w[i] * (double)m[i];
-        s = s + prod;
-    }
-    return s;
-}
-
-template <int MP>
-__device__ __forceinline__ void lane_weights(const double* __restrict__ weights, long long v, bool live, int M, double (&w)[MP]) {
-#pragma unroll
-    for (int m = 0; m < MP; ++m) w[m] = (live && m < M) ? weights[v * M + m] : 0.0;
-}
 
 // wavefronts stride over (tile of the chunk, product) tasks; hdr[1] products (known on the device only)
 template <int MP>
@@ -348,13 +325,7 @@ void launch_joint_chunk(const JointCall& c, const JointWs& j, long long tile0, i
 
 template <int MP>
 void launch_joint_chunk_k(const JointCall& c, const JointWs& j, long long tile0, int tiles, u64* hist) {
-    switch (c.k) {
-        case 1: launch_joint_chunk<1, MP>(c, j, tile0, tiles, hist); break;
-        case 2: launch_joint_chunk<2, MP>(c, j, tile0, tiles, hist); break;
-        case 3: launch_joint_chunk<3, MP>(c, j, tile0, tiles, hist); break;
-        case 4: launch_joint_chunk<4, MP>(c, j, tile0, tiles, hist); break;
-        default: launch_joint_chunk<5, MP>(c, j, tile0, tiles, hist); break;
-    }
+    with_k<MMS_FILTER_MAX_K>(c.k, [&](auto kc) { launch_joint_chunk<decltype(kc)::value, MP>(c, j, tile0, tiles, hist); });
 }
 
 }  // namespace
@@ -390,7 +361,7 @@ void launch_joint_sweep(const int64_t* query_id, const int64_t* product_id, cons
             const RankStats S = launch_rank_stats(query_id, product_id, members, nullptr, n, j.rank, j.rstatus, st);
             (void)hipMemsetAsync(j.pfill, 0, (size_t)j.cap * 4, st);
             const JointCall c{members, M, n, weights, W, filters, (int)G, k, Qa, L, status, st, code_out};
-            const bool mp4 = joint_mp(M) == 4;
+            const bool mp4 = member_mp(M) == 4;
             if (mp4) launch_joint_once<4>(c, j, S);
             else launch_joint_once<8>(c, j, S);
             if (items > 0) {

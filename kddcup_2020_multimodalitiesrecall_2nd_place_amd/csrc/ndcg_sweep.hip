@@ -22,6 +22,7 @@
 //                       operation rounded on its own: ndcg.ndcg_from_hist bit for bit (an empty bin adds +0.0 to a non-negative sum).
 // Integer atomics only, and the order inside a list cannot matter because the selection key (score with -0.0 == +0.0, row) is total: equal inputs give equal bytes.
 #include "rank_tables.h"
+#include "merge_members.h"
 
 #pragma clang fp contract(off)
 
@@ -34,14 +35,12 @@ constexpr int SWEEP_LDS_MAX_K = 5;       // (K + 1) << K bins x 64 lanes x 4 B: 
 template <int MP>
 struct __attribute__((aligned(8 * MP))) SweepRec { float s[MP]; unsigned meta; unsigned pad[MP - 1]; };      // meta = row << 1 | rel
 
-inline int sweep_mp(int M) { return M <= 4 ? 4 : 8; }
-
 struct SweepWs { char* rec; size_t total_bytes; };
 
 SweepWs sweep_layout(void* base, long long n, long long Qa, long long Tk, int M) {
     SweepWs s{};
     Carver cv{(char*)base, up256((size_t)ndcg_workspace_bytes(n, Qa, Tk))};
-    cv.take(s.rec, (size_t)(n > 0 ? n : 1) * (size_t)sweep_mp(M) * 8);
+    cv.take(s.rec, (size_t)(n > 0 ? n : 1) * (size_t)member_mp(M) * 8);
     s.total_bytes = cv.o;
     return s;
 }
@@ -54,15 +53,14 @@ __global__ __launch_bounds__(256) void k_sweep_pack(const float* __restrict__ me
     if (x >= n || x >= status[1]) return;
     const int r = L.list[x];                                                 // inside [0, n): k_scatter wrote it
     SweepRec<MP> o{};
-#pragma unroll
-    for (int m = 0; m < MP; ++m) o.s[m] = m < M ? members[(size_t)m * n + r] : 0.0f;
+    load_members<MP>(members, M, n, r, o.s);
     o.meta = ((unsigned)r << 1) | (unsigned)L.rel[r];                       // r < 2^22
     rec[x] = o;
 }
 
-// The lists are ranked on the scores as doubles (ranks_before<double>).  A non-finite score is flagged, and with a flag the outputs are unspecified.
-// A padded member (m >= M) has score 0 and weight 0: its term adds +0.0, which can change the sign of a zero sum and nothing else -- and -0.0
-// ranks as +0.0.  So the MP-term sum ranks, and flags, exactly as the M-term sum of the contract.
+// The lists are ranked on the scores as doubles (ranks_before<double>), the merge of merge_members.h over the MP padded members.  A non-finite
+// score is flagged, and with a flag the outputs are unspecified.  The kernel spells lane_weights() and merged() out, statement for statement:
+// through the two functions the same loop measured 2 % slower at 176 851 weight vectors (profiles/rd17_fit_family_refactor.txt).
 template <int K, int MP, bool LDS>
 __global__ __launch_bounds__(256) void k_sweep(const double* __restrict__ weights, long long W, int M, int Qa, int slabs, long long tasks, NdcgLists L,
                                                const SweepRec<MP>* __restrict__ rec, u64* hist, int* status) {
@@ -129,12 +127,10 @@ void launch_sweep_mp(hipStream_t st, const float* members, int M, int n, const d
     SweepRec<MP>* rec = (SweepRec<MP>*)records;
     hipLaunchKernelGGL((k_sweep_pack<MP>), dim3((n + 255) / 256), dim3(256), 0, st, members, M, n, L, (const int*)status, rec);
     const SweepGrid g = sweep_grid(W, Qa);
-#define SWEEP_CASE(K) case K: hipLaunchKernelGGL((k_sweep<K, MP, K <= SWEEP_LDS_MAX_K>), dim3(g.grid), dim3(256), 0, st, weights, W, M, Qa, g.slabs, g.tasks, L, rec, hist, status); break
-    switch (k) {
-        SWEEP_CASE(1); SWEEP_CASE(2); SWEEP_CASE(3); SWEEP_CASE(4); SWEEP_CASE(5); SWEEP_CASE(6); SWEEP_CASE(7);
-        default: SWEEP_CASE(8);
-    }
-#undef SWEEP_CASE
+    with_k<MMS_NDCG_MAX_K>(k, [&](auto kc) {
+        constexpr int K = decltype(kc)::value;
+        hipLaunchKernelGGL((k_sweep<K, MP, K <= SWEEP_LDS_MAX_K>), dim3(g.grid), dim3(256), 0, st, weights, W, M, Qa, g.slabs, g.tasks, L, rec, hist, status);
+    });
 }
 
 }  // namespace
@@ -152,7 +148,7 @@ void launch_ndcg_sweep(const int64_t* query_id, const int64_t* product_id, const
         const NdcgLists L = launch_ndcg_lists(query_id, product_id, n, key_query, key_off, key_product, Qa, Tk, allow_missing, workspace, status, st);
         if (n > 0 && W > 0) {
             const SweepWs s = sweep_layout(workspace, n, Qa, Tk, M);
-            if (sweep_mp(M) == 4) launch_sweep_mp<4>(st, members, M, n, weights, W, k, Qa, L, s.rec, (u64*)hist_out, status);
+            if (member_mp(M) == 4) launch_sweep_mp<4>(st, members, M, n, weights, W, k, Qa, L, s.rec, (u64*)hist_out, status);
             else launch_sweep_mp<8>(st, members, M, n, weights, W, k, Qa, L, s.rec, (u64*)hist_out, status);
         }
     }

@@ -5,14 +5,17 @@
 //   lists      block_scan / scan_top (exclusive scan over a workgroup, block sums -> prefixes), scatter_rows (counting-sort scatter by wavefront
 //              runs), ranks_before / wave_next (one round of the wave-wide arg-max selection)
 //   sweeps     TopK (register top-K list of k_sweep; k_filter_sweep writes the same steps out), sweep_task / sweep_zero / sweep_flush / sweep_grid (the (tile, slab) task walk and its
-//              [bins][64] LDS histogram; sweep_flush_strided: the flush of joint_sweep.hip, whose tile's items lie n_filters apart)
+//              [bins][64] LDS histogram; sweep_flush_strided: the flush of joint_sweep.hip, whose tile's items lie n_filters apart),
+//              sweep_flags_of_rank (the rank flags as the submission sweeps report them)
 // Comparisons, integer work and data movement only: the floating-point arithmetic that defines a result stays in the .hip files, below their
-// own fp-contract pragma.  Each translation unit gets its own copy.
+// own fp-contract pragma -- with one exception, the merge of the member scores that two sweeps share: merge_members.h, under a pragma of its
+// own.  Each translation unit gets its own copy.
 #pragma once
 #include "kernels.h"
 #include "../../include/mmscore.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -196,6 +199,17 @@ struct TopK {
         return mask;
     }
 };
+
+// status[2] of launch_rank_stats (mms_rank_submission's bits) as mms_filter_sweep / mms_joint_sweep report it: non-finite (2) and reserved id (8)
+// stay, the repeated pair moves from bit 0 to bit 4 (bit 2, the output overflow, belongs to a stage the sweeps do not run)
+__device__ __forceinline__ int sweep_flags_of_rank(int f) { return (f & 2) | (f & 8) | ((f & 1) << 4); }
+
+// The one switch over a sweep's K: f(std::integral_constant<int, K>) with K = k for k in [1, KMAX] (the entry points check the range; above it: KMAX)
+template <int KMAX, typename F>
+void with_k(int k, F f) {
+    if constexpr (KMAX > 1) { if (k < KMAX) return with_k<KMAX - 1>(k, f); }
+    f(std::integral_constant<int, KMAX>{});
+}
 
 constexpr int SWEEP_MAX_BLOCKS = 4096;   // bounded grid: workgroups stride over the tasks
 constexpr int SWEEP_TARGET_TASKS = 2048; // small grids: the key queries are cut into slabs until there are about this many tasks

@@ -143,12 +143,11 @@ def rank_device(query_id, product_id, score, gap=GAP, tie=TIE):
     Only enqueues on the current stream: nothing is read back, nothing waits."""
     import torch
 
-    from . import lib as _lib
-    from .ndcg import _check_rc, _ptr, _rows_on_device, _score_ptrs
+    from .ndcg import _DeviceCall, _ptr, _rows_on_device, _score_ptrs
     (s, q, p), dev = _rows_on_device((score, query_id, product_id), ((torch.float64, torch.float32), (torch.int64,), (torch.int64,)), "rank_device")
     n = s.shape[0]
-    l = _lib.load()
-    ws_bytes = l.mms_rank_workspace_bytes(n)
+    call = _DeviceCall(dev)
+    ws_bytes = call.l.mms_rank_workspace_bytes(n)
     if ws_bytes < 0:
         raise ValueError("rank_device: %d rows, the device path takes at most MMS_RANK_MAX_ROWS (2^22)" % n)
     m = n                                                                    # at most one output row per input row
@@ -156,11 +155,9 @@ def rank_device(query_id, product_id, score, gap=GAP, tie=TIE):
     out_query = torch.empty((m,), dtype=torch.int64, device=dev)
     out_products = torch.empty((m, 5), dtype=torch.int64, device=dev)
     out_count = torch.empty((m,), dtype=torch.int32, device=dev)
-    status = torch.empty((4,), dtype=torch.int32, device=dev)
-    rc = l.mms_rank_submission(_ptr(q), _ptr(p), *_score_ptrs(s, status), n, float(gap), float(tie), ws.data_ptr(), ws_bytes, m,
-                               _ptr(out_query), _ptr(out_products), _ptr(out_count), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    _check_rc(l, rc, "mms_rank_submission")
-    return out_query, out_products, out_count, status
+    call("mms_rank_submission", _ptr(q), _ptr(p), *_score_ptrs(s, call.status), n, float(gap), float(tie), ws.data_ptr(), ws_bytes, m, _ptr(out_query),
+         _ptr(out_products), _ptr(out_count), call.status.data_ptr())
+    return out_query, out_products, out_count, call.status
 
 
 def submission_rows_device(query_id, product_id, score, gap=GAP, tie=TIE, info=None):
@@ -169,6 +166,8 @@ def submission_rows_device(query_id, product_id, score, gap=GAP, tie=TIE, info=N
     What the device does not do -- a (query, product) pair that occurs twice, a non-finite score, an id equal to the reserved -1 -- it detects:
     the rows then come from ``submission_rows`` on the host arrays.  ``info`` (a dict) receives ``{"path": "device" | "host", "flags": int}``."""
     import torch
+
+    from . import ndcg
     out_query, out_products, out_count, status = rank_device(query_id, product_id, score, gap, tie)
     m = out_query.shape[0]
     g = min(m, max(4096, m // 8))
@@ -178,8 +177,7 @@ def submission_rows_device(query_id, product_id, score, gap=GAP, tie=TIE, info=N
     if info is not None:
         info.update(path="host" if flags else "device", flags=flags)
     if flags:
-        to_np = lambda x: x.detach().cpu().numpy() if torch.is_tensor(x) else x
-        return submission_rows(to_np(query_id), to_np(product_id), to_np(score), gap, tie)
+        return submission_rows(ndcg._to_np(query_id), ndcg._to_np(product_id), ndcg._to_np(score), gap, tie)
     if n_out > g:
         g = n_out
         host = pack(g).cpu().numpy()
@@ -227,28 +225,59 @@ def weight_grid(members: int = 4, steps: int = 20):
     return np.array(rows, np.float64) / steps
 
 
-def _fit(device_call, host_call, use_device, info):
-    """The common half of ``fit_weights`` / ``fit_filter``: the values of every grid row -- from ``device_call() -> (values, _, status)`` with ONE
-    synchronising read when ``use_device`` and the device raises no flag but "missing", else from ``host_call(to_np) -> values`` -- and the FIRST row
-    that attains the maximum.  -> (index, values)."""
+def _check_where(where):
+    if where not in ("host", "device"):
+        raise ValueError("where must be 'host' or 'device', not %r" % (where,))
+
+
+def _weight_rows(grid, M, who):
+    """The weight grid of ``who`` (a ``fit_*`` function's name): float64 [W >= 1, M], ``weight_grid(M, 20)`` by default."""
+    import numpy as np
+    grid = weight_grid(M, 20) if grid is None else np.ascontiguousarray(grid, np.float64)
+    if grid.ndim != 2 or grid.shape[0] == 0:
+        raise ValueError("%s: the grid must be [W >= 1, %d]" % (who, M))
+    return grid
+
+
+def _filter_rows(filters, who):
+    """The filter grid of ``who``: float64 [G >= 1, 2] rows ``(gap, tie)``, ``filter_grid()`` by default."""
+    import numpy as np
+    filters = filter_grid() if filters is None else np.ascontiguousarray(filters, np.float64)
+    if filters.ndim != 2 or filters.shape[1] != 2 or filters.shape[0] == 0:
+        raise ValueError("%s: the filters must be [G >= 1, 2] rows of (gap, tie)" % who)
+    return filters
+
+
+def _joint_result(grid, filters, values, index):
+    """The tuple of ``fit_joint`` for the winner ``index`` of the flat ``values`` [W * G] (weight-major)."""
+    iw, ig = divmod(index, filters.shape[0])
+    return (tuple(float(x) for x in grid[iw]), (float(filters[ig, 0]), float(filters[ig, 1])), float(values[index]), (iw, ig),
+            values.reshape(grid.shape[0], filters.shape[0]))
+
+
+def _fit(device_call, host_call, use_device, info, soft_flags=0):
+    """The common half of the ``fit_*`` functions: the values of every grid point, flat in row-major order -- from ``device_call() -> (values,
+    status, *extras)`` with ONE synchronising read when ``use_device`` and the device raises no flag but "missing" and ``soft_flags``, else from
+    ``host_call() -> values`` -- and the FIRST one that attains the maximum.  ``extras``: further device tensors that ride along in the read.
+    -> (index, values, the extras as one flat float64 numpy array in their order; None on the host path)."""
     import numpy as np
 
     from . import ndcg
-    values, flags = None, 0
+    values, rest, flags = None, None, 0
     if use_device:
         import torch
-        dvalues, _, status = device_call()
-        host = torch.cat([status.to(torch.float64), dvalues]).cpu().numpy()      # the one synchronising read
+        dvalues, status, *extras = device_call()
+        host = torch.cat([x.to(torch.float64).reshape(-1) for x in (status, dvalues, *extras)]).cpu().numpy()   # the one synchronising read
         flags = int(host[2])
-        if flags & ~ndcg.FLAG_MISSING_QUERY == 0:
+        if flags & ~(ndcg.FLAG_MISSING_QUERY | soft_flags) == 0:
             if flags & ndcg.FLAG_MISSING_QUERY:                                  # only without allow_missing
                 raise KeyError("%d key queries have no rows" % int(host[3]))
-            values = host[4:].copy()
+            values, rest = host[4:4 + dvalues.numel()].copy(), host[4 + dvalues.numel():]
     if info is not None:
         info.update(path="device" if values is not None else "host", flags=flags)
     if values is None:
-        values = host_call(lambda x: x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x))
-    return int(np.argmax(values)), values                                        # the first row that attains the maximum
+        values = host_call().reshape(-1)
+    return int(np.argmax(values)), values, rest                                  # the first point that attains the maximum
 
 
 def fit_weights(query_id, product_id, members, rank_label, grid=None, k: int = 5, allow_missing: bool = False, where: str = "device", info: dict = None):
@@ -260,23 +289,14 @@ def fit_weights(query_id, product_id, members, rank_label, grid=None, k: int = 5
     status and the values.  What the device does not do -- a non-finite merged score of a key query's row, a repeated key query, a reserved id --
     it detects: the values then come from ``ndcg.ndcg_sweep_host``, which ``where="host"`` runs directly; both give the same floats, bit for bit.
     A key query without rows raises ``KeyError`` unless ``allow_missing``.  ``info`` (a dict) receives ``{"path": "device" | "host", "flags": int}``."""
-    import numpy as np
-
     from . import ndcg
-    if where not in ("host", "device"):
-        raise ValueError("where must be 'host' or 'device', not %r" % (where,))
-    label_dict = rank_label.rank_label if isinstance(rank_label, ndcg.AnswerKey) else rank_label
-    M = len(members)
-    grid = weight_grid(M, 20) if grid is None else np.ascontiguousarray(grid, np.float64)
-    if grid.ndim != 2 or grid.shape[0] == 0:
-        raise ValueError("fit_weights: the grid must be [W >= 1, %d]" % M)
-
-    def host_call(to_np):
-        mem = np.stack([to_np(m) for m in members]) if isinstance(members, (list, tuple)) else to_np(members)
-        return ndcg.ndcg_sweep_host(to_np(query_id), to_np(product_id), mem, grid, label_dict, k, allow_missing)[0]
-
-    index, values = _fit(lambda: ndcg.ndcg_sweep_device(query_id, product_id, members, grid, rank_label, k, allow_missing), host_call,
-                         where == "device" and len(label_dict), info)
+    _check_where(where)
+    label_dict = ndcg._label_dict(rank_label)
+    grid = _weight_rows(grid, len(members), "fit_weights")
+    index, values, _ = _fit(
+        lambda: ndcg.ndcg_sweep_device(query_id, product_id, members, grid, rank_label, k, allow_missing)[::2],
+        lambda: ndcg.ndcg_sweep_host(ndcg._to_np(query_id), ndcg._to_np(product_id), ndcg._member_array(members), grid, label_dict, k, allow_missing)[0],
+        where == "device" and len(label_dict), info)
     return tuple(float(x) for x in grid[index]), float(values[index]), index, values
 
 
@@ -301,18 +321,14 @@ def fit_filter(query_id, product_id, score, rank_label, filters=None, k: int = 5
     and the values.  What the device does not do -- a (query, product) pair that occurs twice, a non-finite score in any row, a repeated key query,
     a reserved id -- it detects: the values then come from ``ndcg.filter_sweep_host``, which ``where="host"`` runs directly; both give the same
     floats, bit for bit.  A key query without rows raises ``KeyError`` unless ``allow_missing``.  ``info`` receives ``{"path", "flags"}``."""
-    import numpy as np
-
     from . import ndcg
-    if where not in ("host", "device"):
-        raise ValueError("where must be 'host' or 'device', not %r" % (where,))
-    label_dict = rank_label.rank_label if isinstance(rank_label, ndcg.AnswerKey) else rank_label
-    filters = filter_grid() if filters is None else np.ascontiguousarray(filters, np.float64)
-    if filters.ndim != 2 or filters.shape[1] != 2 or filters.shape[0] == 0:
-        raise ValueError("fit_filter: the filters must be [G >= 1, 2] rows of (gap, tie)")
-    index, values = _fit(lambda: ndcg.filter_sweep_device(query_id, product_id, score, filters, rank_label, k, allow_missing),
-                         lambda to_np: ndcg.filter_sweep_host(to_np(query_id), to_np(product_id), to_np(score), filters, label_dict, k, allow_missing)[0],
-                         where == "device" and len(label_dict), info)
+    _check_where(where)
+    label_dict = ndcg._label_dict(rank_label)
+    filters = _filter_rows(filters, "fit_filter")
+    index, values, _ = _fit(
+        lambda: ndcg.filter_sweep_device(query_id, product_id, score, filters, rank_label, k, allow_missing)[::2],
+        lambda: ndcg.filter_sweep_host(ndcg._to_np(query_id), ndcg._to_np(product_id), ndcg._to_np(score), filters, label_dict, k, allow_missing)[0],
+        where == "device" and len(label_dict), info)
     return (float(filters[index, 0]), float(filters[index, 1])), float(values[index]), index, values
 
 
@@ -327,33 +343,15 @@ def fit_joint(query_id, product_id, members, rank_label, grid=None, filters=None
     values.  What the device does not do -- a (query, product) pair that occurs twice, a non-finite merged score in any row, a repeated key query, a
     reserved id -- it detects: the values then come from ``ndcg.joint_sweep_host``, which ``where="host"`` runs directly; both give the same floats,
     bit for bit.  A key query without rows raises ``KeyError`` unless ``allow_missing``.  ``info`` receives ``{"path", "flags"}``."""
-    import numpy as np
-
     from . import ndcg
-    if where not in ("host", "device"):
-        raise ValueError("where must be 'host' or 'device', not %r" % (where,))
-    label_dict = rank_label.rank_label if isinstance(rank_label, ndcg.AnswerKey) else rank_label
-    M = len(members)
-    grid = weight_grid(M, 20) if grid is None else np.ascontiguousarray(grid, np.float64)
-    if grid.ndim != 2 or grid.shape[0] == 0:
-        raise ValueError("fit_joint: the grid must be [W >= 1, %d]" % M)
-    filters = filter_grid() if filters is None else np.ascontiguousarray(filters, np.float64)
-    if filters.ndim != 2 or filters.shape[1] != 2 or filters.shape[0] == 0:
-        raise ValueError("fit_joint: the filters must be [G >= 1, 2] rows of (gap, tie)")
-    W, G = grid.shape[0], filters.shape[0]
-
-    def device_call():
-        values, _, status = ndcg.joint_sweep_device(query_id, product_id, members, grid, filters, rank_label, k, allow_missing)
-        return values.reshape(-1), None, status
-
-    def host_call(to_np):
-        mem = np.stack([to_np(m) for m in members]) if isinstance(members, (list, tuple)) else to_np(members)
-        return ndcg.joint_sweep_host(to_np(query_id), to_np(product_id), mem, grid, filters, label_dict, k, allow_missing)[0].reshape(-1)
-
-    index, values = _fit(device_call, host_call, where == "device" and len(label_dict), info)
-    iw, ig = divmod(index, G)
-    return (tuple(float(x) for x in grid[iw]), (float(filters[ig, 0]), float(filters[ig, 1])), float(values[index]), (iw, ig),
-            values.reshape(W, G))
+    _check_where(where)
+    label_dict = ndcg._label_dict(rank_label)
+    grid, filters = _weight_rows(grid, len(members), "fit_joint"), _filter_rows(filters, "fit_joint")
+    index, values, _ = _fit(
+        lambda: ndcg.joint_sweep_device(query_id, product_id, members, grid, filters, rank_label, k, allow_missing)[::2],
+        lambda: ndcg.joint_sweep_host(ndcg._to_np(query_id), ndcg._to_np(product_id), ndcg._member_array(members), grid, filters, label_dict, k, allow_missing)[0],
+        where == "device" and len(label_dict), info)
+    return _joint_result(grid, filters, values, index)
 
 
 # ---- resampling the joint fit: held-out nDCG@k of the (weights, gap, tie) that fit_joint selects ----
@@ -411,16 +409,10 @@ def fit_joint_resampled(query_id, product_id, members, rank_label, grid=None, fi
     import numpy as np
 
     from . import ndcg
-    if where not in ("host", "device"):
-        raise ValueError("where must be 'host' or 'device', not %r" % (where,))
-    label_dict = rank_label.rank_label if isinstance(rank_label, ndcg.AnswerKey) else rank_label
-    M, Qa = len(members), len(label_dict)
-    grid = weight_grid(M, 20) if grid is None else np.ascontiguousarray(grid, np.float64)
-    if grid.ndim != 2 or grid.shape[0] == 0:
-        raise ValueError("fit_joint_resampled: the grid must be [W >= 1, %d]" % M)
-    filters = filter_grid() if filters is None else np.ascontiguousarray(filters, np.float64)
-    if filters.ndim != 2 or filters.shape[1] != 2 or filters.shape[0] == 0:
-        raise ValueError("fit_joint_resampled: the filters must be [G >= 1, 2] rows of (gap, tie)")
+    _check_where(where)
+    label_dict = ndcg._label_dict(rank_label)
+    Qa = len(label_dict)
+    grid, filters = _weight_rows(grid, len(members), "fit_joint_resampled"), _filter_rows(filters, "fit_joint_resampled")
     W, G = grid.shape[0], filters.shape[0]
     code_bytes = G * Qa * ((W + 63) // 64 * 64)
     if code_bytes > code_budget:
@@ -442,38 +434,31 @@ def fit_joint_resampled(query_id, product_id, members, rank_label, grid=None, fi
     user_items = np.array([a * G + b for a, b in probes], np.int64)
     P = 1 + len(probes)
 
-    values, res, flags = None, None, 0
-    if where == "device" and Qa:
+    def device_call():
         import torch
-        dvalues, _, status, codes = ndcg.joint_codes_device(query_id, product_id, members, grid, filters, rank_label, k, allow_missing)
-        flat = dvalues.reshape(-1)
-        # the whole-key winner, the first item at the maximum, stays on the device as probe 0 (index plumbing on [W * G]; the read below checks it)
+        values, _, status, codes = ndcg.joint_codes_device(query_id, product_id, members, grid, filters, rank_label, k, allow_missing)
+        flat = values.reshape(-1)
+        # the whole-key winner, the first item at the maximum, stays on the device as probe 0 (index plumbing on [W * G]; checked after the read)
         first = torch.where(flat == flat.max(), torch.arange(W * G, device=flat.device), W * G).min().reshape(1)
         items = torch.cat([first, torch.from_numpy(user_items).to(flat.device)])
-        best, fv, ev, pf, pe, _ = ndcg.resample_select_device(codes, W, count_fit, count_eval, k, items, status)
-        host = torch.cat([status.to(torch.float64), first.to(torch.float64), flat, best.to(torch.float64), fv, ev, pf.reshape(-1), pe.reshape(-1)]).cpu().numpy()   # the one synchronising read
-        flags = int(host[2])
-        if flags & ~(ndcg.FLAG_MISSING_QUERY | ndcg.FLAG_EMPTY_FIT) == 0:
-            if flags & ndcg.FLAG_MISSING_QUERY:                                  # only without allow_missing
-                raise KeyError("%d key queries have no rows" % int(host[3]))
-            o = 5 + W * G
-            values = host[5:o].copy()
-            res = (host[o:o + R].astype(np.int64), host[o + R:o + 2 * R].copy(), host[o + 2 * R:o + 3 * R].copy(),
-                   host[o + 3 * R:o + 3 * R + R * P].reshape(R, P).copy(), host[o + 3 * R + R * P:].reshape(R, P).copy())
-            if int(host[4]) != int(np.argmax(values)):
-                raise RuntimeError("fit_joint_resampled: probe 0 is item %d, the whole-key winner item %d" % (int(host[4]), int(np.argmax(values))))
-    if info is not None:
-        info.update(path="device" if values is not None else "host", flags=flags)
-    if values is None:
-        to_np = lambda x: x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
-        mem = np.stack([to_np(m) for m in members]) if isinstance(members, (list, tuple)) else to_np(members)
-        qh, ph = to_np(query_id), to_np(product_id)
-        values = ndcg.joint_sweep_host(qh, ph, mem, grid, filters, label_dict, k, allow_missing)[0].reshape(-1)
+        return (flat, status, first) + ndcg.resample_select_device(codes, W, count_fit, count_eval, k, items, status)[:5]
+
+    def host_call():
+        qh, ph, mem = ndcg._to_np(query_id), ndcg._to_np(product_id), ndcg._member_array(members)
+        values = ndcg.joint_sweep_host(qh, ph, mem, grid, filters, label_dict, k, allow_missing)[0]
         codes = ndcg.joint_codes_host(qh, ph, mem, grid, filters, label_dict, k, allow_missing)
-        res = ndcg.resample_select_host(codes, count_fit, count_eval, k, np.r_[np.int64(np.argmax(values)), user_items])
-    index = int(np.argmax(values))                                               # the first item that attains the maximum
+        res.extend(ndcg.resample_select_host(codes, count_fit, count_eval, k, np.r_[np.int64(np.argmax(values)), user_items]))
+        return values
+
+    res = []
+    index, values, rest = _fit(device_call, host_call, where == "device" and Qa, info, soft_flags=ndcg.FLAG_EMPTY_FIT)
+    if rest is not None:                                                         # first [1], best, fit, eval [R], probe_fit, probe_eval [R, P]
+        if int(rest[0]) != index:
+            raise RuntimeError("fit_joint_resampled: probe 0 is item %d, the whole-key winner item %d" % (int(rest[0]), index))
+        best, fv, ev, pf, pe = np.split(rest[1:], np.cumsum([R, R, R, R * P]))
+        res = [best.astype(np.int64), fv.copy(), ev.copy(), pf.reshape(R, P).copy(), pe.reshape(R, P).copy()]
     iw, ig = divmod(index, G)
-    whole = (tuple(float(x) for x in grid[iw]), (float(filters[ig, 0]), float(filters[ig, 1])), float(values[index]), (iw, ig), values.reshape(W, G))
+    whole = _joint_result(grid, filters, values, index)
     best, fit_values, eval_values, probe_fit, probe_eval = res
     winners = np.where(best[:, None] >= 0, np.stack([best // G, best % G], 1), -1)
     gap = fit_values - eval_values
@@ -518,22 +503,18 @@ def cascade_keep_device(query_id, stage1, keep: int, info: dict = None):
     keeps every row; the result then comes from the host form.  ``info`` receives ``{"path", "flags", "n_kept", "queries", "largest_query"}``."""
     import torch
 
-    from . import lib as _lib
-    from .ndcg import _check_rc, _ptr, _rows_on_device
+    from .ndcg import _DeviceCall, _ptr, _rows_on_device
     (s, q), dev = _rows_on_device((stage1, query_id), ((torch.float32,), (torch.int64,)), "cascade_keep_device")
     n = s.shape[0]
-    l = _lib.load()
-    ws_bytes = l.mms_cascade_workspace_bytes(n)
+    call = _DeviceCall(dev)
+    ws_bytes = call.l.mms_cascade_workspace_bytes(n)
     if ws_bytes < 0:
         raise ValueError("cascade_keep_device: %d rows" % n)
     ws = torch.empty((max(ws_bytes, 256),), dtype=torch.uint8, device=dev)
     kept = torch.empty((n,), dtype=torch.uint8, device=dev)
     kept_list = torch.empty((n,), dtype=torch.int32, device=dev)
-    status = torch.empty((4,), dtype=torch.int32, device=dev)
-    rc = l.mms_cascade_select(_ptr(q), _ptr(s), n, int(keep), _ptr(kept), _ptr(kept_list), status.data_ptr(), ws.data_ptr(), ws_bytes,
-                              torch.cuda.current_stream(dev).cuda_stream)
-    _check_rc(l, rc, "mms_cascade_select")
-    flags, n_kept, queries, largest = (int(v) for v in status.cpu().numpy())         # the one synchronising read
+    call("mms_cascade_select", _ptr(q), _ptr(s), n, int(keep), _ptr(kept), _ptr(kept_list), call.status.data_ptr(), ws.data_ptr(), ws_bytes)
+    flags, n_kept, queries, largest = (int(v) for v in call.status.cpu().numpy())    # the one synchronising read
     if info is not None:
         info.update(path="host" if flags else "device", flags=flags, n_kept=n_kept, queries=queries, largest_query=largest)
     if flags:
@@ -570,10 +551,8 @@ def cascade_curve(query_id, product_id, members, rank_label, keeps, weights=WEIG
     import numpy as np
 
     from . import ndcg
-    if where not in ("host", "device"):
-        raise ValueError("where must be 'host' or 'device', not %r" % (where,))
-    to_np = lambda x: x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
-    q, p, mem = to_np(query_id).astype(np.int64), to_np(product_id).astype(np.int64), np.asarray(to_np(members), np.float32)
+    _check_where(where)
+    q, p, mem = ndcg._to_np(query_id).astype(np.int64), ndcg._to_np(product_id).astype(np.int64), np.asarray(ndcg._to_np(members), np.float32)
     n = len(q)
     grid = np.array([weights], np.float64)
     filters = np.array([[gap, tie]], np.float64)

@@ -138,12 +138,27 @@ class AnswerKey:
         self.n_queries, self.n_products = len(keys), int(prod.shape[0])
 
 
-def _key_on(rank_label, dev):
+def _label_dict(rank_label):
+    """The ``{query: [products]}`` dict of a ``rank_label`` argument: the dict itself, or the one an ``AnswerKey`` was built from."""
+    return rank_label.rank_label if isinstance(rank_label, AnswerKey) else rank_label
+
+
+def _to_np(x):
+    """A tensor (wherever it lives) or an array-like as a numpy array: what the host forms take."""
+    return x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x)
+
+
+def _key_on(rank_label, dev, what=None):
+    """The answer key on ``dev``; with ``what`` (the caller's name) an empty key is an error."""
     if isinstance(rank_label, AnswerKey):
         if rank_label.device != dev:
             raise ValueError("the AnswerKey lives on %s, the rows on %s" % (rank_label.device, dev))
-        return rank_label
-    return AnswerKey(rank_label, dev)
+        key = rank_label
+    else:
+        key = AnswerKey(rank_label, dev)
+    if what is not None and key.n_queries == 0:
+        raise ValueError("%s: empty answer key" % what)
+    return key
 
 
 def _rows_on_device(arrays, dtypes, what):
@@ -161,6 +176,12 @@ def _rows_on_device(arrays, dtypes, what):
     return out, dev
 
 
+def _on_device(x, dev, dtype):
+    """``x`` as a contiguous tensor of ``dtype`` on ``dev``: used in place when it already is one, a host array is copied up once."""
+    import torch
+    return (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).to(device=dev, dtype=dtype, non_blocking=True).contiguous()
+
+
 def _workspace(ws_bytes, n, key, dev, what):
     """The workspace of ``ws_bytes`` (what a ``mms_*_workspace_bytes`` returned: negative for a table beyond the limits) -> (tensor, ws_bytes)."""
     import torch
@@ -171,6 +192,7 @@ def _workspace(ws_bytes, n, key, dev, what):
 
 
 _ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+_key_args = lambda key: (_ptr(key.key_query), _ptr(key.key_off), _ptr(key.key_product), key.n_queries, key.n_products)      # the CSR answer key, as every entry point takes it
 
 
 def _score_ptrs(s, status):
@@ -186,25 +208,38 @@ def _check_rc(l, rc, name):
         raise _lib.MmsError("%s failed (%d): %s" % (name, rc, l.mms_global_error().decode()))
 
 
+class _DeviceCall:
+    """What every wrapper of a handle-free entry point needs around its one call: the library ``l`` (for the ``*_workspace_bytes`` query too), a
+    ``status`` block int32 [4] on ``dev`` (the caller's, or a fresh one the call writes), the current stream and the check of the return code.
+    Where the status pointer goes among the arguments is the entry point's business."""
+
+    def __init__(self, dev, status=None):
+        import torch
+
+        from . import lib as _lib
+        self.l, self.dev = _lib.load(), dev
+        self.status = torch.empty((4,), dtype=torch.int32, device=dev) if status is None else status
+
+    def __call__(self, name, *args):
+        """``l.<name>(*args, stream)``: ``args`` is everything in front of the stream, which every entry point takes last.  Only enqueues."""
+        import torch
+        _check_rc(self.l, getattr(self.l, name)(*args, torch.cuda.current_stream(self.dev).cuda_stream), name)
+
+
 def relevance_device(query_id, product_id, rank_label, status_out: list = None):
     """The ground-truth labels of the rows on the GPU (``mms_key_relevance``): int64 device tensor [n], 1 where the row's product is in its query's
     truth list.  ``rank_label``: the ``{query: [products]}`` dict or an ``AnswerKey``.  Only enqueues on the current stream; ``status_out`` (a list)
     receives the device status tensor [4] (rows of key queries in [1], flags in [2]) for a caller that wants to read it later."""
     import torch
-
-    from . import lib as _lib
     (q, p), dev = _rows_on_device((query_id, product_id), ((torch.int64,), (torch.int64,)), "relevance_device")
     key = _key_on(rank_label, dev)
     n = q.shape[0]
-    l = _lib.load()
-    ws, ws_bytes = _workspace(l.mms_ndcg_workspace_bytes(n, key.n_queries, key.n_products), n, key, dev, "relevance_device")
+    call = _DeviceCall(dev)
+    ws, ws_bytes = _workspace(call.l.mms_ndcg_workspace_bytes(n, key.n_queries, key.n_products), n, key, dev, "relevance_device")
     labels = torch.empty((n,), dtype=torch.int64, device=dev)
-    status = torch.empty((4,), dtype=torch.int32, device=dev)
-    rc = l.mms_key_relevance(_ptr(q), _ptr(p), n, _ptr(key.key_query), _ptr(key.key_off), _ptr(key.key_product), key.n_queries, key.n_products,
-                             ws.data_ptr(), ws_bytes, _ptr(labels), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    _check_rc(l, rc, "mms_key_relevance")
+    call("mms_key_relevance", _ptr(q), _ptr(p), n, *_key_args(key), ws.data_ptr(), ws_bytes, _ptr(labels), call.status.data_ptr())
     if status_out is not None:
-        status_out.append(status)
+        status_out.append(call.status)
     return labels
 
 
@@ -213,24 +248,19 @@ def ndcg_codes_device(query_id, product_id, score, rank_label, k: int = 5, allow
     -> (codes int32 [Qa], topk int64 [Qa, k] or None, hist int64 [(k + 1) << k], status int32 [4]), device tensors.  Only enqueues on the
     current stream: nothing is read back, nothing waits."""
     import torch
-
-    from . import lib as _lib
     if not 1 <= k <= MAX_K:
         raise ValueError("k must be in 1..%d" % MAX_K)
     (q, p, s), dev = _rows_on_device((query_id, product_id, score), ((torch.int64,), (torch.int64,), (torch.float64, torch.float32)), "ndcg_device")
     key = _key_on(rank_label, dev)
     n = s.shape[0]
-    l = _lib.load()
-    ws, ws_bytes = _workspace(l.mms_ndcg_workspace_bytes(n, key.n_queries, key.n_products), n, key, dev, "ndcg_device")
+    call = _DeviceCall(dev)
+    ws, ws_bytes = _workspace(call.l.mms_ndcg_workspace_bytes(n, key.n_queries, key.n_products), n, key, dev, "ndcg_device")
     codes = torch.empty((key.n_queries,), dtype=torch.int32, device=dev)
     topk = torch.empty((key.n_queries, k), dtype=torch.int64, device=dev) if want_topk else None
     hist = torch.empty(((k + 1) << k,), dtype=torch.int64, device=dev)
-    status = torch.empty((4,), dtype=torch.int32, device=dev)
-    rc = l.mms_ndcg_at_k(_ptr(q), _ptr(p), *_score_ptrs(s, status), n, _ptr(key.key_query), _ptr(key.key_off), _ptr(key.key_product),
-                         key.n_queries, key.n_products, k, int(bool(allow_missing)), ws.data_ptr(), ws_bytes, _ptr(codes), _ptr(topk), hist.data_ptr(),
-                         status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    _check_rc(l, rc, "mms_ndcg_at_k")
-    return codes, topk, hist, status
+    call("mms_ndcg_at_k", _ptr(q), _ptr(p), *_score_ptrs(s, call.status), n, *_key_args(key), k, int(bool(allow_missing)), ws.data_ptr(), ws_bytes,
+         _ptr(codes), _ptr(topk), hist.data_ptr(), call.status.data_ptr())
+    return codes, topk, hist, call.status
 
 
 def ndcg_device(query_id, product_id, score, rank_label, k: int = 5, info: dict = None, allow_missing: bool = False, return_hist: bool = False):
@@ -242,7 +272,7 @@ def ndcg_device(query_id, product_id, score, rank_label, k: int = 5, info: dict 
     What the device does not do -- a non-finite score, a repeated key query, an id equal to the reserved -1 -- it detects: the value then
     comes from the host form on the host arrays.  ``info`` (a dict) receives ``{"path": "device" | "host", "flags": int}``."""
     import torch
-    label_dict = rank_label.rank_label if isinstance(rank_label, AnswerKey) else rank_label
+    label_dict = _label_dict(rank_label)
     if len(label_dict) == 0:
         return ndcg_from_arrays([], [], [], label_dict, k)                   # the host form's own error for an empty key
     codes, _, hist, status = ndcg_codes_device(query_id, product_id, score, rank_label, k, allow_missing)
@@ -252,8 +282,7 @@ def ndcg_device(query_id, product_id, score, rank_label, k: int = 5, info: dict 
     if info is not None:
         info.update(path="host" if flags & ~FLAG_MISSING_QUERY else "device", flags=flags)
     if flags & ~FLAG_MISSING_QUERY:
-        to_np = lambda x: x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
-        qh, ph, sh = to_np(query_id), to_np(product_id), to_np(score)
+        qh, ph, sh = _to_np(query_id), _to_np(product_id), _to_np(score)
         if return_hist:
             c = ndcg_codes(qh, ph, sh, label_dict, k, allow_missing)
             return hist_from_codes(c, k), int((c >= 0).sum())
@@ -318,11 +347,10 @@ def ndcg_sweep_host(query_id, product_id, members, weights, rank_label: dict, k:
     """The host form of the sweep and the reference of the device form: per weight vector ``hist_from_codes(ndcg_codes(q, p, merge_members(members,
     w), ...))`` and ``ndcg_from_hist`` of it over the whole key.  ``members``: float32 [M, n] (member-major, the layout ``mms_score_ensemble`` writes),
     ``weights``: float64 [W, M].  -> (values float64 [W], hist int64 [W, (k + 1) << k]), numpy."""
-    mem = np.stack([np.asarray(m).reshape(-1) for m in members]) if isinstance(members, (list, tuple)) and members else np.asarray(members)
-    mem = mem.astype(np.float32) if mem.dtype != np.float32 else mem
+    mem = _member_array(members)
     wts = np.asarray(weights, np.float64)
     _sweep_args(mem, wts, k)
-    label_dict = rank_label.rank_label if isinstance(rank_label, AnswerKey) else rank_label
+    label_dict = _label_dict(rank_label)
     mem = mem.reshape(mem.shape[0], -1)
     values = np.empty(wts.shape[0], np.float64)
     hist = np.empty((wts.shape[0], (k + 1) << k), np.int64)
@@ -339,31 +367,20 @@ def ndcg_sweep_device(query_id, product_id, members, weights, rank_label, k: int
     device tensors, bit-equal to ``ndcg_sweep_host`` while the flag word ``status[2]`` is zero (or "missing" alone with ``allow_missing``).
     Only enqueues on the current stream: nothing is read back, nothing waits."""
     import torch
-
-    from . import lib as _lib
     (q, p), dev = _rows_on_device((query_id, product_id), ((torch.int64,), (torch.int64,)), "ndcg_sweep_device")
-    to_t = lambda x, dt: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).to(device=dev, dtype=dt, non_blocking=True).contiguous()
-    if isinstance(members, (list, tuple)):
-        members = torch.stack([to_t(m, torch.float32).reshape(-1) for m in members]) if members else torch.zeros((0, 0))
-    mem, wts = to_t(members, torch.float32), to_t(weights, torch.float64)
+    mem, wts = _members_on(members, dev), _on_device(weights, dev, torch.float64)
     _sweep_args(mem, wts, k)
     n, M, W = q.shape[0], mem.shape[0], wts.shape[0]
     if mem.shape[1] != n:
         raise ValueError("ndcg_sweep_device: %d rows, member scores of %d" % (n, mem.shape[1]))
-    key = _key_on(rank_label, dev)
-    if key.n_queries == 0:
-        raise ValueError("ndcg_sweep_device: empty answer key")
-    l = _lib.load()
-    ws, ws_bytes = _workspace(l.mms_ndcg_sweep_workspace_bytes(n, key.n_queries, key.n_products, M), n, key, dev, "ndcg_sweep_device")
-    table = _bin_table(k, dev)
+    key = _key_on(rank_label, dev, "ndcg_sweep_device")
+    call = _DeviceCall(dev)
+    ws, ws_bytes = _workspace(call.l.mms_ndcg_sweep_workspace_bytes(n, key.n_queries, key.n_products, M), n, key, dev, "ndcg_sweep_device")
     hist = torch.empty((W, (k + 1) << k), dtype=torch.int64, device=dev)
     values = torch.empty((W,), dtype=torch.float64, device=dev)
-    status = torch.empty((4,), dtype=torch.int32, device=dev)
-    rc = l.mms_ndcg_weight_sweep(_ptr(q), _ptr(p), _ptr(mem), M, n, _ptr(key.key_query), _ptr(key.key_off), _ptr(key.key_product), key.n_queries,
-                                 key.n_products, _ptr(wts), W, k, int(bool(allow_missing)), table.data_ptr(), key.n_queries, ws.data_ptr(), ws_bytes,
-                                 _ptr(hist), _ptr(values), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    _check_rc(l, rc, "mms_ndcg_weight_sweep")
-    return values, hist, status
+    call("mms_ndcg_weight_sweep", _ptr(q), _ptr(p), _ptr(mem), M, n, *_key_args(key), _ptr(wts), W, k, int(bool(allow_missing)),
+         _bin_table(k, dev).data_ptr(), key.n_queries, ws.data_ptr(), ws_bytes, _ptr(hist), _ptr(values), call.status.data_ptr())
+    return values, hist, call.status
 
 
 # ---- filter sweep: nDCG@k of the SUBMISSION rows for every (gap, tie) pair of a grid (mms_filter_sweep, csrc/filter_sweep.hip) ----
@@ -406,7 +423,7 @@ def submission_codes(query_id, product_id, score, rank_label: dict, gap, tie, k:
     ``mask`` set when the j-th product of the output row is in ``set(truth)`` (j < min(k, products written)), ``ideal = min(len(set(truth)), k)``."""
     from . import ensemble
     _filter_k(k)
-    label_dict = rank_label.rank_label if isinstance(rank_label, AnswerKey) else rank_label
+    label_dict = _label_dict(rank_label)
     q = np.asarray(query_id).astype(np.int64).reshape(-1)
     rows = ensemble.submission_rows(q, np.asarray(product_id).reshape(-1), np.asarray(score).reshape(-1), gap, tie)
     return codes_of_rows(rows, set(np.unique(q).tolist()), label_dict, k, allow_missing)
@@ -421,13 +438,22 @@ def _filter_array(filters):
     return f
 
 
+def _filters_on(filters, dev):
+    """The filter grid as a float64 [G, 2] tensor on ``dev`` (a host array through ``_filter_array``'s checks first)."""
+    import torch
+    flt = _on_device(filters if torch.is_tensor(filters) else _filter_array(filters), dev, torch.float64)
+    if flt.ndim != 2 or flt.shape[1] != 2 or flt.shape[0] > MAX_FILTERS:
+        raise ValueError("filters must be [G <= %d, 2] rows of (gap, tie), not %s" % (MAX_FILTERS, tuple(flt.shape)))
+    return flt
+
+
 def filter_sweep_host(query_id, product_id, score, filters, rank_label: dict, k: int = 5, allow_missing: bool = False):
     """The host form of the filter sweep and the reference of the device form: per row ``(gap, tie)`` of ``filters`` (float64 [G, 2])
     ``submission_codes``, the histogram of the codes >= 0 and ``ndcg_from_hist`` of it over the WHOLE key -- a dropped or missing query costs its
     share, as a grader of the submission file charges it.  -> (values float64 [G], hist int64 [G, (k + 1) << k], codes int32 [G, Qa]), numpy."""
     f = _filter_array(filters)
     _filter_k(k)
-    label_dict = rank_label.rank_label if isinstance(rank_label, AnswerKey) else rank_label
+    label_dict = _label_dict(rank_label)
     G, Qa = f.shape[0], len(label_dict)
     values = np.empty(G, np.float64)
     hist = np.empty((G, (k + 1) << k), np.int64)
@@ -446,30 +472,19 @@ def filter_sweep_device(query_id, product_id, score, filters, rank_label, k: int
     ``filter_sweep_host`` -- integers entry for entry, values bit for bit -- while the flag word ``status[2]`` is zero.
     Only enqueues on the current stream: nothing is read back, nothing waits."""
     import torch
-
-    from . import lib as _lib
     _filter_k(k)
     (q, p, s), dev = _rows_on_device((query_id, product_id, score), ((torch.int64,), (torch.int64,), (torch.float64, torch.float32)), "filter_sweep_device")
-    flt = filters if torch.is_tensor(filters) else torch.from_numpy(_filter_array(filters))
-    flt = flt.to(device=dev, dtype=torch.float64, non_blocking=True).contiguous()
-    if flt.ndim != 2 or flt.shape[1] != 2 or flt.shape[0] > MAX_FILTERS:
-        raise ValueError("filters must be [G <= %d, 2] rows of (gap, tie), not %s" % (MAX_FILTERS, tuple(flt.shape)))
-    key = _key_on(rank_label, dev)
-    if key.n_queries == 0:
-        raise ValueError("filter_sweep_device: empty answer key")
+    flt = _filters_on(filters, dev)
+    key = _key_on(rank_label, dev, "filter_sweep_device")
     n, G = s.shape[0], flt.shape[0]
-    l = _lib.load()
-    ws, ws_bytes = _workspace(l.mms_filter_sweep_workspace_bytes(n, key.n_queries, key.n_products), n, key, dev, "filter_sweep_device")
-    table = _bin_table(k, dev)
+    call = _DeviceCall(dev)
+    ws, ws_bytes = _workspace(call.l.mms_filter_sweep_workspace_bytes(n, key.n_queries, key.n_products), n, key, dev, "filter_sweep_device")
     hist = torch.empty((G, (k + 1) << k), dtype=torch.int64, device=dev)
     values = torch.empty((G,), dtype=torch.float64, device=dev)
     codes = torch.empty((G, key.n_queries), dtype=torch.int32, device=dev) if want_codes else None
-    status = torch.empty((4,), dtype=torch.int32, device=dev)
-    rc = l.mms_filter_sweep(_ptr(q), _ptr(p), *_score_ptrs(s, status), n, _ptr(key.key_query), _ptr(key.key_off), _ptr(key.key_product),
-                            key.n_queries, key.n_products, _ptr(flt), G, k, int(bool(allow_missing)), table.data_ptr(), key.n_queries, ws.data_ptr(), ws_bytes,
-                            _ptr(hist), _ptr(values), _ptr(codes), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    _check_rc(l, rc, "mms_filter_sweep")
-    return (values, hist, status, codes) if want_codes else (values, hist, status)
+    call("mms_filter_sweep", _ptr(q), _ptr(p), *_score_ptrs(s, call.status), n, *_key_args(key), _ptr(flt), G, k, int(bool(allow_missing)),
+         _bin_table(k, dev).data_ptr(), key.n_queries, ws.data_ptr(), ws_bytes, _ptr(hist), _ptr(values), _ptr(codes), call.status.data_ptr())
+    return (values, hist, call.status, codes) if want_codes else (values, hist, call.status)
 
 
 # ---- joint sweep: nDCG@k of the SUBMISSION rows for every (weight vector, filter) pair (mms_joint_sweep, csrc/joint_sweep.hip) ----
@@ -478,8 +493,17 @@ JOINT_STATS_BYTES = 256 << 20             # joint_sweep_device's default chunk: 
 
 
 def _member_array(members):
-    mem = np.stack([np.asarray(m).reshape(-1) for m in members]) if isinstance(members, (list, tuple)) and members else np.asarray(members)
+    """The member scores (an array or tensor [M, n], or a list of M rows, wherever they live) as one float32 numpy array."""
+    mem = np.stack([_to_np(m).reshape(-1) for m in members]) if isinstance(members, (list, tuple)) and members else _to_np(members)
     return mem.astype(np.float32) if mem.dtype != np.float32 else mem
+
+
+def _members_on(members, dev):
+    """The member scores as one float32 tensor on ``dev``: a list of rows is stacked, a [M, n] device tensor is used in place."""
+    import torch
+    if isinstance(members, (list, tuple)):
+        members = torch.stack([_on_device(m, dev, torch.float32).reshape(-1) for m in members]) if members else torch.zeros((0, 0))
+    return _on_device(members, dev, torch.float32)
 
 
 def _joint_args(members, weights, n_filters, k):
@@ -489,17 +513,18 @@ def _joint_args(members, weights, n_filters, k):
         raise ValueError("at most %d (weight vector, filter) pairs per call" % MAX_JOINT_ITEMS)
 
 
+def _joint_host_args(members, weights, filters, rank_label, k):
+    mem, wts, f = _member_array(members), np.asarray(weights, np.float64), _filter_array(filters)
+    _joint_args(mem, wts, f.shape[0], k)
+    return mem.reshape(mem.shape[0], -1), wts, f, _label_dict(rank_label)
+
+
 def joint_sweep_host(query_id, product_id, members, weights, filters, rank_label: dict, k: int = 5, allow_missing: bool = False):
     """The host form of the joint sweep and the reference of the device form -- by definition the loop: per weight vector ``w`` of ``weights``
     (float64 [W, M]) ``filter_sweep_host`` of ``filters`` (float64 [G, 2] rows ``(gap, tie)``) on ``merge_members(members, w)``.  It composes the two
     existing contracts (the merge of the weight sweep feeds the filter sweep unchanged) and adds no arithmetic of its own.  ``members``: float32
     [M, n], member-major.  -> (values float64 [W, G], hist int64 [W, G, (k + 1) << k]), numpy."""
-    mem = _member_array(members)
-    wts = np.asarray(weights, np.float64)
-    f = _filter_array(filters)
-    _joint_args(mem, wts, f.shape[0], k)
-    label_dict = rank_label.rank_label if isinstance(rank_label, AnswerKey) else rank_label
-    mem = mem.reshape(mem.shape[0], -1)
+    mem, wts, f, label_dict = _joint_host_args(members, weights, filters, rank_label, k)
     values = np.empty((wts.shape[0], f.shape[0]), np.float64)
     hist = np.empty((wts.shape[0], f.shape[0], (k + 1) << k), np.int64)
     for v in range(wts.shape[0]):
@@ -523,47 +548,33 @@ def joint_sweep_device(query_id, product_id, members, weights, filters, rank_lab
 def _joint_sweep_call(query_id, product_id, members, weights, filters, rank_label, k, allow_missing, want_hist, chunk_tiles, want_codes):
     """``joint_sweep_device`` (``mms_joint_sweep``) or, with ``want_codes``, ``joint_codes_device`` (``mms_joint_sweep_codes``: the codes come fourth)."""
     import torch
-
-    from . import lib as _lib
     (q, p), dev = _rows_on_device((query_id, product_id), ((torch.int64,), (torch.int64,)), "joint_sweep_device")
-    to_t = lambda x, dt: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).to(device=dev, dtype=dt, non_blocking=True).contiguous()
-    if isinstance(members, (list, tuple)):
-        members = torch.stack([to_t(m, torch.float32).reshape(-1) for m in members]) if members else torch.zeros((0, 0))
-    mem, wts = to_t(members, torch.float32), to_t(weights, torch.float64)
-    flt = to_t(filters if torch.is_tensor(filters) else _filter_array(filters), torch.float64)
-    if flt.ndim != 2 or flt.shape[1] != 2 or flt.shape[0] > MAX_FILTERS:
-        raise ValueError("filters must be [G <= %d, 2] rows of (gap, tie), not %s" % (MAX_FILTERS, tuple(flt.shape)))
+    mem, wts, flt = _members_on(members, dev), _on_device(weights, dev, torch.float64), _filters_on(filters, dev)
     _joint_args(mem, wts, flt.shape[0], k)
     n, M, W, G = q.shape[0], mem.shape[0], wts.shape[0], flt.shape[0]
     if mem.shape[1] != n:
         raise ValueError("joint_sweep_device: %d rows, member scores of %d" % (n, mem.shape[1]))
-    key = _key_on(rank_label, dev)
-    if key.n_queries == 0:
-        raise ValueError("joint_sweep_device: empty answer key")
+    key = _key_on(rank_label, dev, "joint_sweep_device")
     if chunk_tiles is not None and chunk_tiles < 1:
         raise ValueError("joint_sweep_device: chunk_tiles must be >= 1")
-    l = _lib.load()
+    call = _DeviceCall(dev)
     bins = (k + 1) << k
     tiles = max(1, (W + 63) // 64)
     chunk = min(tiles, max(1, JOINT_STATS_BYTES // (16 * 64 * max(n, 1))) if chunk_tiles is None else int(chunk_tiles))
-    ws_bytes = l.mms_joint_sweep_workspace_bytes(n, key.n_queries, key.n_products, M, chunk)
+    ws_bytes = call.l.mms_joint_sweep_workspace_bytes(n, key.n_queries, key.n_products, M, chunk)
     if ws_bytes >= 0 and not want_hist:
         ws_bytes += chunk * ((64 * G * bins * 8 + 255) & ~255)                 # the chunk's histograms
     ws, ws_bytes = _workspace(ws_bytes, n, key, dev, "joint_sweep_device")
-    table = _bin_table(k, dev)
     hist = torch.empty((W, G, bins), dtype=torch.int64, device=dev) if want_hist else None
     values = torch.empty((W, G), dtype=torch.float64, device=dev)
-    status = torch.empty((4,), dtype=torch.int32, device=dev)
-    args = (_ptr(q), _ptr(p), _ptr(mem), M, n, _ptr(key.key_query), _ptr(key.key_off), _ptr(key.key_product), key.n_queries, key.n_products, _ptr(wts), W,
-            _ptr(flt), G, k, int(bool(allow_missing)), table.data_ptr(), key.n_queries, ws.data_ptr(), ws_bytes, _ptr(hist), _ptr(values))
-    if want_codes:
-        codes = torch.empty((G, key.n_queries, (W + 63) // 64 * 64), dtype=torch.uint8, device=dev)
-        rc = l.mms_joint_sweep_codes(*args, _ptr(codes), codes.numel(), status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-        _check_rc(l, rc, "mms_joint_sweep_codes")
-        return values, hist, status, codes
-    rc = l.mms_joint_sweep(*args, status.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    _check_rc(l, rc, "mms_joint_sweep")
-    return values, hist, status
+    args = (_ptr(q), _ptr(p), _ptr(mem), M, n, *_key_args(key), _ptr(wts), W, _ptr(flt), G, k, int(bool(allow_missing)), _bin_table(k, dev).data_ptr(),
+            key.n_queries, ws.data_ptr(), ws_bytes, _ptr(hist), _ptr(values))
+    if not want_codes:
+        call("mms_joint_sweep", *args, call.status.data_ptr())
+        return values, hist, call.status
+    codes = torch.empty((G, key.n_queries, (W + 63) // 64 * 64), dtype=torch.uint8, device=dev)
+    call("mms_joint_sweep_codes", *args, _ptr(codes), codes.numel(), call.status.data_ptr())
+    return values, hist, call.status, codes
 
 
 # ---- resampling the joint fit: byte codes per (vector, filter, key query) and replicates of counts over the key (mms_joint_sweep_codes,
@@ -605,12 +616,7 @@ def _byte_table(k, dev):
 def joint_codes_host(query_id, product_id, members, weights, filters, rank_label: dict, k: int = 5, allow_missing: bool = False):
     """The host form of the code matrix of ``mms_joint_sweep_codes`` and its reference: per weight vector ``w`` and filter ``(gap, tie)`` the bytes of
     ``submission_codes`` on ``merge_members(members, w)``.  -> uint8 numpy [W, G, Qa] (item-major: ``[v, g]`` are the codes of item ``v * G + g``)."""
-    mem = _member_array(members)
-    wts = np.asarray(weights, np.float64)
-    f = _filter_array(filters)
-    _joint_args(mem, wts, f.shape[0], k)
-    label_dict = rank_label.rank_label if isinstance(rank_label, AnswerKey) else rank_label
-    mem = mem.reshape(mem.shape[0], -1)
+    mem, wts, f, label_dict = _joint_host_args(members, weights, filters, rank_label, k)
     out = np.empty((wts.shape[0], f.shape[0], len(label_dict)), np.uint8)
     for v in range(wts.shape[0]):
         merged = merge_members(mem, wts[v])
@@ -699,8 +705,6 @@ def resample_select_device(codes, n_weights: int, count_fit, count_eval, k: int 
     once).  -> (best int64 [R], fit_value [R], eval_value [R], probe_fit [R, P], probe_eval [R, P], status), device tensors, equal to
     ``resample_select_host`` -- winners entry for entry, values bit for bit.  Only enqueues on the current stream."""
     import torch
-
-    from . import lib as _lib
     _filter_k(k)
     if not torch.is_tensor(codes) or codes.dtype != torch.uint8 or codes.ndim != 3 or not codes.is_cuda or not codes.is_contiguous():
         raise ValueError("codes must be the contiguous uint8 [G, Qa, Wp] device tensor of joint_codes_device")
@@ -709,28 +713,22 @@ def resample_select_device(codes, n_weights: int, count_fit, count_eval, k: int 
     W = int(n_weights)
     if W < 0 or Wp != (W + 63) // 64 * 64:
         raise ValueError("resample_select_device: %d weight vectors do not match codes of %s" % (W, tuple(codes.shape)))
-    to_u8 = lambda x: (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))).to(dev, non_blocking=True).contiguous()
-    cf, ce = to_u8(count_fit), to_u8(count_eval)
+    cf, ce = _on_device(count_fit, dev, None), _on_device(count_eval, dev, None)              # (dtype None: kept, and checked below)
     if cf.dtype != torch.uint8 or ce.dtype != torch.uint8 or cf.ndim != 2 or cf.shape != ce.shape or cf.shape[1] != Qa:
         raise ValueError("count_fit / count_eval must be uint8 [R, %d], not %s %s / %s %s" % (Qa, cf.dtype, tuple(cf.shape), ce.dtype, tuple(ce.shape)))
     R = cf.shape[0]
-    pr = probes if torch.is_tensor(probes) else torch.from_numpy(_probe_array(probes))
-    pr = pr.to(device=dev, dtype=torch.int64, non_blocking=True).contiguous().reshape(-1)
+    pr = _on_device(probes if torch.is_tensor(probes) else _probe_array(probes), dev, torch.int64).reshape(-1)
     P = pr.shape[0]
     if R > MAX_REPLICATES or P > MAX_PROBES:
         raise ValueError("at most %d replicates and %d probes per call" % (MAX_REPLICATES, MAX_PROBES))
-    l = _lib.load()
-    ws_bytes = l.mms_resample_workspace_bytes(W, G, Qa, R)
+    call = _DeviceCall(dev, torch.zeros((4,), dtype=torch.int32, device=dev) if status is None else status)      # (the flags are ORed in)
+    ws_bytes = call.l.mms_resample_workspace_bytes(W, G, Qa, R)
     if ws_bytes < 0:
         raise ValueError("resample_select_device: %d x %d items, %d key queries, %d replicates: beyond the limits of mms_resample_select" % (W, G, Qa, R))
     ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-    if status is None:
-        status = torch.zeros((4,), dtype=torch.int32, device=dev)
     best = torch.empty((R,), dtype=torch.int64, device=dev)
     fit_value, eval_value = (torch.empty((R,), dtype=torch.float64, device=dev) for _ in range(2))
     probe_fit, probe_eval = (torch.empty((R, P), dtype=torch.float64, device=dev) for _ in range(2))
-    rc = l.mms_resample_select(_ptr(codes), codes.numel(), W, G, Qa, _ptr(cf), _ptr(ce), R, _byte_table(k, dev).data_ptr(), _ptr(pr), P, ws.data_ptr(),
-                               ws_bytes, _ptr(best), _ptr(fit_value), _ptr(eval_value), _ptr(probe_fit), _ptr(probe_eval), status.data_ptr(),
-                               torch.cuda.current_stream(dev).cuda_stream)
-    _check_rc(l, rc, "mms_resample_select")
-    return best, fit_value, eval_value, probe_fit, probe_eval, status
+    call("mms_resample_select", _ptr(codes), codes.numel(), W, G, Qa, _ptr(cf), _ptr(ce), R, _byte_table(k, dev).data_ptr(), _ptr(pr), P, ws.data_ptr(),
+         ws_bytes, _ptr(best), _ptr(fit_value), _ptr(eval_value), _ptr(probe_fit), _ptr(probe_eval), call.status.data_ptr())
+    return best, fit_value, eval_value, probe_fit, probe_eval, call.status

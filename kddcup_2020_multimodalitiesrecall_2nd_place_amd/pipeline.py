@@ -476,6 +476,30 @@ class EnsembleScorer:
                 self._cascade_info(info, kept[0], offsets)
         return qid, pid, out
 
+    def _merged_pass(self, tsv_path, vocab_path, label_table, rank_label, labels, batch_pairs, threads, feat_decode, scores_out, metric="device",
+                     cascade_keep=None, info=None):
+        """A pass over a valid file that leaves the MERGED scores on the device, the zk members' label feed as ``labels`` says: -> (query_id,
+        product_id, score fp64 [n], the relabelled key); ``scores_out`` receives ``query_id`` / ``product_id`` / ``score``."""
+        _check_eval_args(metric, labels)
+        rank_label, relabel = _relabel(labels, rank_label, self.zk.device)
+        qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=False, relabel=relabel,
+                                       cascade_keep=cascade_keep, info=info)
+        score = torch.cat([m for m, _ in out]).double() if out else torch.zeros(0, dtype=torch.float64, device=self.zk.device)
+        if scores_out is not None:
+            scores_out.update(query_id=qid, product_id=pid, score=score)
+        return qid, pid, score, rank_label
+
+    def _member_pass(self, tsv_path, vocab_path, label_table, rank_label, labels, batch_pairs, threads, feat_decode, scores_out):
+        """The same pass with the four MEMBER scores left on the device: -> (query_id, product_id, members fp32 [4, n], the pass's batch offsets,
+        the relabelled key); ``scores_out`` receives ``query_id`` / ``product_id`` / ``members``."""
+        _check_eval_args("device", labels)
+        rank_label, relabel = _relabel(labels, rank_label, self.zk.device)
+        qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=True, relabel=relabel)
+        mem = torch.cat([m for _, m in out], 1) if out else torch.zeros((4, 0), dtype=torch.float32, device=self.zk.device)
+        if scores_out is not None:
+            scores_out.update(query_id=qid, product_id=pid, members=mem)
+        return qid, pid, mem, np.cumsum([0] + [int(m.shape[0]) for m, _ in out]).tolist(), rank_label
+
     def evaluate_tsv_native(self, tsv_path, vocab_path, label_table, rank_label, k: int = 5, metric: str = "device", labels: str = "answer",
                             batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host", info: dict = None, scores_out: dict = None,
                             cascade_keep: int = None):
@@ -484,13 +508,8 @@ class EnsembleScorer:
         (``labels="answer"``) or all ones (``labels="ones"``, today's feed), the metric on the GPU (``metric="device"``) or by
         ``ndcg.ndcg_from_arrays`` on the fp64 copy of the scores (``metric="host"``) -- the same float.  ``cascade_keep``: the cascade form of
         the fused call (``_tsv_pass``); ``info`` also receives ``cascade_kept`` / ``cascade_pairs`` / ``batch_offsets``."""
-        _check_eval_args(metric, labels)
-        rank_label, relabel = _relabel(labels, rank_label, self.zk.device)
-        qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=False, relabel=relabel,
-                                       cascade_keep=cascade_keep, info=info)
-        score = torch.cat([m for m, _ in out]).double() if out else torch.zeros(0, dtype=torch.float64, device=self.zk.device)
-        if scores_out is not None:
-            scores_out.update(query_id=qid, product_id=pid, score=score)
+        qid, pid, score, rank_label = self._merged_pass(tsv_path, vocab_path, label_table, rank_label, labels, batch_pairs, threads, feat_decode, scores_out,
+                                                        metric, cascade_keep, info)
         return _metric(qid, pid, score, rank_label, k, metric, False, info)
 
     def fit_weights_tsv_native(self, tsv_path, vocab_path, label_table, rank_label, grid=None, k: int = 5, labels: str = "answer",
@@ -503,12 +522,7 @@ class EnsembleScorer:
         The value of a weight vector is that of main.py's DOUBLE merge of the fp32 member scores; ``evaluate_tsv_native`` ranks the fp32 merge
         of the fused call, which can differ on a near tie."""
         from . import ensemble
-        _check_eval_args("device", labels)
-        rank_label, relabel = _relabel(labels, rank_label, self.zk.device)
-        qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=True, relabel=relabel)
-        mem = torch.cat([m for _, m in out], 1) if out else torch.zeros((4, 0), dtype=torch.float32, device=self.zk.device)
-        if scores_out is not None:
-            scores_out.update(query_id=qid, product_id=pid, members=mem)
+        qid, pid, mem, _, rank_label = self._member_pass(tsv_path, vocab_path, label_table, rank_label, labels, batch_pairs, threads, feat_decode, scores_out)
         return ensemble.fit_weights(qid, pid, mem, rank_label, grid, k, info=info)
 
     def fit_filter_tsv_native(self, tsv_path, vocab_path, label_table, rank_label, filters=None, k: int = 5, labels: str = "answer",
@@ -519,12 +533,7 @@ class EnsembleScorer:
         -> ((gap, tie), value, index, values numpy [G]), the tuple of ``fit_filter``; pass the winner to ``submission_tsv_native(gap=, tie=)``.
         ``scores_out`` (a dict) receives ``query_id`` / ``product_id`` (numpy) and ``score`` (device fp64)."""
         from . import ensemble
-        _check_eval_args("device", labels)
-        rank_label, relabel = _relabel(labels, rank_label, self.zk.device)
-        qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=False, relabel=relabel)
-        score = torch.cat([m for m, _ in out]).double() if out else torch.zeros(0, dtype=torch.float64, device=self.zk.device)
-        if scores_out is not None:
-            scores_out.update(query_id=qid, product_id=pid, score=score)
+        qid, pid, score, rank_label = self._merged_pass(tsv_path, vocab_path, label_table, rank_label, labels, batch_pairs, threads, feat_decode, scores_out)
         return ensemble.fit_filter(qid, pid, score, rank_label, filters, k, info=info)
 
     def fit_joint_tsv_native(self, tsv_path, vocab_path, label_table, rank_label, grid=None, filters=None, k: int = 5, labels: str = "answer",
@@ -538,12 +547,7 @@ class EnsembleScorer:
         ``product_id`` (numpy) and ``members`` (device fp32 [4, n]).  The value is that of main.py's DOUBLE merge of the fp32 member scores; the
         fused call ranks the fp32 merge, which can differ on a near tie."""
         from . import ensemble
-        _check_eval_args("device", labels)
-        rank_label, relabel = _relabel(labels, rank_label, self.zk.device)
-        qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=True, relabel=relabel)
-        mem = torch.cat([m for _, m in out], 1) if out else torch.zeros((4, 0), dtype=torch.float32, device=self.zk.device)
-        if scores_out is not None:
-            scores_out.update(query_id=qid, product_id=pid, members=mem)
+        qid, pid, mem, _, rank_label = self._member_pass(tsv_path, vocab_path, label_table, rank_label, labels, batch_pairs, threads, feat_decode, scores_out)
         return ensemble.fit_joint(qid, pid, mem, rank_label, grid, filters, k, info=info)
 
     def fit_joint_resampled_tsv_native(self, tsv_path, vocab_path, label_table, rank_label, grid=None, filters=None, k: int = 5, labels: str = "answer",
@@ -555,12 +559,7 @@ class EnsembleScorer:
         ``fit_joint_resampled``: ``whole`` is the tuple of ``fit_joint_tsv_native``; ``heldout``, ``optimism`` and ``agreement`` say how far to trust
         it.  The scorer's own weights are NOT changed.  ``scores_out`` as in ``fit_joint_tsv_native``."""
         from . import ensemble
-        _check_eval_args("device", labels)
-        rank_label, relabel = _relabel(labels, rank_label, self.zk.device)
-        qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=True, relabel=relabel)
-        mem = torch.cat([m for _, m in out], 1) if out else torch.zeros((4, 0), dtype=torch.float32, device=self.zk.device)
-        if scores_out is not None:
-            scores_out.update(query_id=qid, product_id=pid, members=mem)
+        qid, pid, mem, _, rank_label = self._member_pass(tsv_path, vocab_path, label_table, rank_label, labels, batch_pairs, threads, feat_decode, scores_out)
         return ensemble.fit_joint_resampled(qid, pid, mem, rank_label, grid, filters, k, info=info, **resample)
 
     def cascade_curve_tsv_native(self, tsv_path, vocab_path, label_table, rank_label, keeps, gap: float = None, tie: float = None, k: int = 5,
@@ -572,13 +571,10 @@ class EnsembleScorer:
         whose row changes.  Choose ``keep`` here, then pass it as ``cascade_keep`` to ``submission_tsv_native`` with the same ``batch_pairs``.
         ``scores_out`` receives ``query_id`` / ``product_id`` (numpy), ``members`` (device fp32 [4, n]) and ``batch_offsets``."""
         from . import ensemble
-        _check_eval_args("device", labels)
-        rank_label, relabel = _relabel(labels, rank_label, self.zk.device)
-        qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=True, relabel=relabel)
-        mem = torch.cat([m for _, m in out], 1) if out else torch.zeros((4, 0), dtype=torch.float32, device=self.zk.device)
-        offsets = np.cumsum([0] + [int(m.shape[0]) for m, _ in out]).tolist()
+        qid, pid, mem, offsets, rank_label = self._member_pass(tsv_path, vocab_path, label_table, rank_label, labels, batch_pairs, threads, feat_decode,
+                                                               scores_out)
         if scores_out is not None:
-            scores_out.update(query_id=qid, product_id=pid, members=mem, batch_offsets=offsets)
+            scores_out["batch_offsets"] = offsets
         gap, tie = ensemble.GAP if gap is None else gap, ensemble.TIE if tie is None else tie
         return ensemble.cascade_curve(qid, pid, mem, rank_label, keeps, self.weights, gap, tie, k, parts=offsets, where=where)
 
