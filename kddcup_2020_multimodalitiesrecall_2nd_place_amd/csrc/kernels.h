@@ -358,3 +358,6 @@ long long resample_workspace_bytes(long long n_weights, long long n_filters, lon
 void launch_resample_select(const uint8_t* code, long long n_weights, long long n_filters, int Qa, const uint8_t* count_fit, const uint8_t* count_eval,
                             int n_replicates, const double* byte_value, const int64_t* probe_item, int n_probes, void* workspace, int64_t* best,
                             double* fit_value, double* eval_value, double* probe_fit, double* probe_eval, int32_t* status, hipStream_t st);
+
+// api.hip: sets the thread-local message mms_global_error() returns -- for the handle-free test hooks (test_hooks.hip).  Hidden: not an export of the library
+__attribute__((visibility("hidden"))) void set_global_error(const char* msg);

@@ -163,8 +163,8 @@ int main(void) {
 
 
 def test_header_lists_the_size_regime_bounds_the_library_uses():
-    """csrc/regimes.h is the ONE table of launch-size bounds and engine numbers: include/mmscore.h carries it verbatim (generated), api.hip and
-    gemm_dispatch.hip define no bound of their own and compare engines by name, lib.py mirrors the enum."""
+    """csrc/regimes.h is the ONE table of launch-size bounds and engine numbers: include/mmscore.h carries it verbatim (generated), api.hip,
+    test_hooks.hip and gemm_dispatch.hip define no bound of their own and compare engines by name, lib.py mirrors the enum."""
     import importlib.util
     spec = importlib.util.spec_from_file_location("gen_regime_doc", os.path.join(ROOT, "tools", "gen_regime_doc.py"))
     gen = importlib.util.module_from_spec(spec)
@@ -180,7 +180,8 @@ def test_header_lists_the_size_regime_bounds_the_library_uses():
         assert re.search(r"rows\s+%s\s+%d\s+%s\b" % (re.escape(t[1]), t[3], t[0]), hdr), t[0]
     csrc = os.path.join(ROOT, "kddcup_2020_multimodalitiesrecall_2nd_place_amd", "csrc")
     api, disp = open(os.path.join(csrc, "api.hip")).read(), open(os.path.join(csrc, "gemm_dispatch.hip")).read()
-    for src in (api, disp):                            # no second definition of a bound, no engine compared by number
+    hooks = open(os.path.join(csrc, "test_hooks.hip")).read()
+    for src in (api, disp, hooks):                     # no second definition of a bound, no engine compared by number
         for name in consts:
             assert not re.search(r"constexpr\s+int(?:64_t)?\s+%s\s*=" % name, src), name
         assert not re.search(r"\b(?:variant|engine|e)\s*[!=]=\s*\d", src)
@@ -203,3 +204,18 @@ def test_test_hooks_are_fenced_out_of_the_product_header(tmp_path):
     assert hooks.returncode == 0, hooks.stderr
     src.write_text('#include "mmscore.h"\nint main(void) { return mms_version() == MMS_ABI_VERSION ? 0 : 1; }\n')
     assert subprocess.run(["gcc", "-I", hdr, "-fsyntax-only", "-Wall", "-Werror", str(src)], capture_output=True, text=True).returncode == 0
+
+
+def test_the_handle_free_hooks_live_in_their_own_file_behind_one_resource_frame():
+    """csrc/test_hooks.hip: device memory and events are acquired and released by the guard types alone (DbgPool, DbgEvents), so no return path of a hook can
+    leak; api.hip keeps only the hooks that read an mms_handle."""
+    csrc = os.path.join(ROOT, "kddcup_2020_multimodalitiesrecall_2nd_place_amd", "csrc")
+    hooks, api = open(os.path.join(csrc, "test_hooks.hip")).read(), open(os.path.join(csrc, "api.hip")).read()
+    for call, guard in (("hipMalloc(", "DbgPool"), ("hipFree(", "DbgPool"), ("hipEventCreate(", "DbgEvents"), ("hipEventDestroy(", "DbgEvents")):
+        assert hooks.count(call) == 1, call
+        body = re.search(r"struct %s \{.*?\n\};" % guard, hooks, flags=re.S).group(0)
+        assert call in body, (call, guard)
+    moved = r"mms_dbg_(?:gemm|attention|layernorm|proj_ln)\w*|mms_dbg_(?:qkv_attn|pack_plan|dedup|convert|splitk_reduce)"
+    assert not re.search(r"^\w[\w\s\*]*\b(?:%s)\s*\(" % moved, api, flags=re.M), "api.hip still defines a handle-free hook"
+    for name in sorted(set(re.findall(r"\b(?:%s)\b" % moved, open(os.path.join(ROOT, "include", "mmscore.h")).read()))):
+        assert re.search(r"^int %s\(" % name, hooks, flags=re.M), name      # ... and test_hooks.hip defines every one the header declares
