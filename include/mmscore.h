@@ -674,7 +674,8 @@ int mms_dbg_qkv_attn(const float* x, int64_t rows1, int64_t rows2, const int32_t
 /* launch counters since mms_create: which = 0 -> fused QKV + attention launches (mms_config.fuse_attention took effect), 1 -> GEMM launches
  * with the fused LayerNorm epilogue (mms_config.fuse_layernorm), 2 -> split-K launches of the small-call routes, 3 -> skinny-GEMM launches (launches of <= 128
  * padded rows, precision modes 2 and 3), 4 -> fork / join pairs of the second launch lane (lxmert handles; on a zk handle: the member lanes of mms_score_ensemble);
- * anything else: -1 */
+ * 5 -> not a launch counter: the bytes of device memory the handle holds NOW (weights, workspaces, partials: the sum over its pools -- a warmed-up handle's figure
+ * does not move from call to call); anything else: -1 */
 int64_t mms_dbg_counter(mms_handle* h, int32_t which);
 int mms_dbg_layernorm(const float* x, const float* gamma, const float* beta, int64_t M, float* out_f32, void* stream);
 /* ONE launch of the small-sequence attention kernel (attn.hip) in the forms the forwards use.  q / k / v: device fp32, already in the layout `flags` names; B pairs;

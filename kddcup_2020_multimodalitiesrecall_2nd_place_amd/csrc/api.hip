@@ -36,6 +36,47 @@ struct Planes {
     }
 };
 
+// Owns one group of the handle's device buffers (the idiom of DbgPool, test_hooks.hip): EVERY device buffer of a handle belongs to a DevPool member, so
+// destroying the handle frees them all.  A rebuild reads: compare with cap, clear(), one get per buffer, done().  A failed allocation comes back as nullptr
+// and is remembered; nothing is allocated after it, and done() gives the partial blocks back.
+struct DevPool {
+    std::vector<void*> blocks;
+    int64_t cap = 0;                   // what the pool is sized for (pairs, rows, floats: its ensure_* routine's unit); 0 while it is being rebuilt
+    size_t held = 0;                   // bytes in `blocks`
+    hipError_t err = hipSuccess;       // the first failure, and the call that met it as HIP_TRY would print it
+    const char* what = "";
+    DevPool() = default;
+    DevPool(const DevPool&) = delete;
+    DevPool& operator=(const DevPool&) = delete;
+    ~DevPool() { clear(); }
+    void clear() {                     // (freeing waits for the work that may still read the blocks)
+        for (void* p : blocks) (void)hipFree(p);
+        blocks.clear();
+        cap = 0; held = 0; err = hipSuccess;
+    }
+    bool ok() const { return err == hipSuccess; }
+    template <typename T>
+    T* get(int64_t n) {                // n ELEMENTS of T
+        if (!ok()) return nullptr;
+        const size_t bytes = (size_t)n * sizeof(T);
+        void* p = nullptr;
+#define POOL_CALL(expr) (what = #expr, err = (expr))
+        if (POOL_CALL(hipMalloc(&p, bytes ? bytes : 16)) != hipSuccess) return nullptr;
+#undef POOL_CALL
+        blocks.push_back(p);
+        held += bytes ? bytes : 16;
+        return (T*)p;
+    }
+    Planes planes(int64_t elems) {     // hl32: one buffer of 2 * elems, 32-element blocks of hi and lo alternating (common.h)
+        Planes p;
+        p.hi = get<bf16>(2 * elems);
+        if (p.hi) p.lo = p.hi + MMS_PLANE_LO;
+        return p;
+    }
+    int fail(mms_handle* h);                 // reports err on the handle (MMS_ERR_HIP) and forgets it; the blocks stay
+    int done(mms_handle* h, int64_t n);      // closes a rebuild: on an error clear() + fail(), else cap = n
+};
+
 // *8 / *s: e4m3 copy of the matrix (8 x 128-byte tiles) and its per-output-channel scales as packed e8m0 bytes (precision mode 4 only)
 struct AttW { bf16* wqkv; float* bqkv; bf16* wo; float* bo; float* g; float* b; unsigned char* wqkv8 = nullptr; unsigned* wqkvs = nullptr;
               unsigned char* wo8 = nullptr; unsigned* wos = nullptr;
@@ -60,7 +101,6 @@ struct mms_handle {
     mms_config cfg{};
     std::string err;
     std::unordered_map<std::string, HostTensor> host;
-    std::vector<void*> w_allocs, ws_allocs, lab_allocs;
     bool finalized = false;
     int nsplit = 2;
     bool f8 = false;       // precision mode 4: the big encoder GEMMs run on e4m3 operands; everything else as mode 2
@@ -71,6 +111,20 @@ struct mms_handle {
     int x1_mask = 0;   // lab build only (env MMS_X1_MASK): GEMM classes forced to one pass: 1 qkv, 2 att-out, 4 ffn-up, 8 ffn-down
     struct WPlane { const bf16* base; long long elems; };
     std::vector<WPlane> w_planes;   // precision 3: hi plane [base, base+elems), lo plane right behind it
+
+    // ---- device memory: every buffer pointer below points into one of these pools (delete frees them; held() is their sum, mms_dbg_counter 5) ----
+    DevPool w_mem;                                   // weights (+ the timing counters)
+    DevPool ws_mem, kparts_mem, kparts_side_mem;     // chunk workspace and the split-K partials of the two lanes, sized with it
+    DevPool lab_mem, dd_mem;                         // label-text encoder, label-tuple de-duplication
+    DevPool lq_mem, lq_store_mem, lq_sub_mem;        // lxmert distinct-query stage: per-pair tables, output store, gather buffers of one sub-batch
+    DevPool ens_mem, ens_c_mem, ens_tok_mem, ens_featp_mem;      // fused three-model call: feeds and outputs, changed-query buffers of the second zk member, image tokens, split box features
+    DevPool cas_mem, cas_g_mem;                      // cascade: selection, gathered second-stage batch
+    size_t held() const {
+        size_t n = 0;
+        for (const DevPool* p : {&w_mem, &ws_mem, &kparts_mem, &kparts_side_mem, &lab_mem, &dd_mem, &lq_mem, &lq_store_mem, &lq_sub_mem, &ens_mem, &ens_c_mem,
+                                 &ens_tok_mem, &ens_featp_mem, &cas_mem, &cas_g_mem}) n += p->held;
+        return n;
+    }
 
     // ---- weights (device) ----
     float *E = nullptr, *type_tab = nullptr, *pos_tab = nullptr, *emb_g = nullptr, *emb_b = nullptr;
@@ -88,8 +142,7 @@ struct mms_handle {
           *be_box = nullptr, *w_lconv = nullptr, *b_lconv = nullptr, *b_labfc = nullptr, *g_lab = nullptr, *be_lab = nullptr,
           *b_fc0 = nullptr, *g_fc2 = nullptr, *be_fc2 = nullptr, *w_fc3 = nullptr, *b_fc3 = nullptr;
 
-    // ---- workspace (device), sized for ws_pairs ----
-    int64_t ws_pairs = 0;
+    // ---- workspace (device), sized for ws_mem.cap pairs ----
     Planes x, ctx, y, mid;
     float *qkv = nullptr, *t = nullptr, *key_add = nullptr, *key_add2 = nullptr, *pooled = nullptr, *hbuf = nullptr;
     int64_t x_rows = 0;  // rows of the hidden state per pair-chunk (for mms_debug_read_x)
@@ -102,7 +155,7 @@ struct mms_handle {
     float* ln_stats = nullptr; int* ln_ctl = nullptr; int ln_slot = 0; unsigned ln_tag = 0;
 
     static constexpr int LN_SLOTS = 2048;
-    float* kparts = nullptr; int64_t kparts_floats = 0;    // fp32 partials of the split-K launches (small calls): slices x launch rows x N, sized with the workspace (ensure_kparts)
+    float* kparts = nullptr;    // fp32 partials of the split-K launches (small calls): slices x launch rows x N, sized with the workspace (ensure_kparts)
     // Second launch lane (lxmert calls below LANE_ROWS token rows): the language and the vision stream's sub-layers between two cross attentions -- and the
     // distinct-query stage beside the box stream's layers -- are independent chains of under-filled launches; the vision chain / the query stage is enqueued on `side`
     // between a fork and a join event.  Same kernels on the same operands: results do not change.  lane == 1 while the side chain is being enqueued: its split-K partials
@@ -110,25 +163,22 @@ struct mms_handle {
     hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool no_fused_ln = false;      // this call takes the two-kernel LayerNorm route throughout: it runs on lanes -- or WOULD without per-launch timing (the route must not depend on instrumentation)
     int lane = 0; bool lanes_on = false, lanes_q = false;      // lanes_on: the whole call (stream chains of the X layers, language beside box layers); lanes_q: the distinct-query stage only
-    float* kparts_side = nullptr; int64_t kparts_side_floats = 0; int64_t mid_side_off = 0, mid_elems = 0;
+    float* kparts_side = nullptr; int64_t mid_side_off = 0, mid_elems = 0;
     int fuse_ln = 0;       // mms_config.fuse_layernorm (lab build: env MMS_FUSE_LN overrides)
     int fuse_attn = 0;     // mms_config.fuse_attention: QKV projection + self-attention in one kernel (qkv_attn.hip; precision mode 2)
     int* qa_rec[3] = {nullptr, nullptr, nullptr};      // per-pair records of the tables (split-bf16 attention route)
     int* qa_jump = nullptr;                            // scratch of the plan kernel (jump tables)
     int4* qa_sub[4] = {nullptr, nullptr, nullptr, nullptr}; int* qa_nsub = nullptr;     // sub-tile tables of the (up to two) token streams of a launch wave; [2], [3]: the CROSS table of the stream pair (lxmert X layers)
-    // label-text workspace, sized for lab_cap unique labels
+    // label-text workspace: lab_feat holds lab_mem.cap unique labels, the encoder's buffers one wave of lab_cap of them
     int64_t lab_cap = 0;
-    Planes lab_planes; float *lab_f32 = nullptr, *lab_feat = nullptr; int64_t lab_feat_cap = 0;
+    Planes lab_planes; float *lab_f32 = nullptr, *lab_feat = nullptr;
     int64_t n_labels = 0;  // rows of lab_feat that are valid for the current call
-    // label-tuple de-duplication workspace (dense label ids), sized for dd_rows = B*10 tuples
-    std::vector<void*> dd_allocs;
-    int64_t dd_rows = 0; int dd_cap = 0;
+    // label-tuple de-duplication workspace (dense label ids), sized for dd_mem.cap = B*10 tuples
+    int dd_cap = 0;
     int *dd_slots = nullptr, *dd_rep = nullptr, *dd_uid = nullptr, *dd_counter = nullptr, *dd_index = nullptr;
     int32_t* dd_uniq32 = nullptr; int64_t* dd_uniq64 = nullptr;
     // lxmert distinct-query stage: the language stream of the first l_layers runs once per distinct (input_ids, input_mask)
     // row; lq_store holds its output rows, dense by (query, token), for the pair chunks to copy from
-    std::vector<void*> lq_allocs, lq_sub_allocs;      // lq_sub_allocs: the two sub-batch gather buffers (replaced, not piled up, when they grow)
-    int64_t lq_pairs = 0, lq_store_q = 0, lq_sub = 0;
     int *lq_slots = nullptr, *lq_rep = nullptr, *lq_uid = nullptr, *lq_counter = nullptr, *lq_rows_of = nullptr, *lq_index = nullptr;
     int lq_cap = 0;
     int64_t *lq_ids = nullptr, *lq_mask = nullptr;
@@ -137,22 +187,18 @@ struct mms_handle {
     bool lq_join_pending = false;                      // the stage was enqueued on the side lane: lx_chunk joins before it reads lq_store
     Planes lq_store;
     bool lq_active = false;
-    // fused three-model entry point: feed conversions and member outputs, sized for ens_pairs
-    std::vector<void*> ens_allocs, ens_c_allocs;      // ens_c_allocs: the changed-query buffers of the second zk member (replaced when they grow)
-    int64_t ens_pairs = 0;
+    // fused three-model entry point: feed conversions and member outputs, sized for ens_mem.cap pairs
     int32_t* ens_seg = nullptr; int64_t *ens_ids64 = nullptr, *ens_seg64 = nullptr, *ens_lab64 = nullptr, *ens_mask64 = nullptr;
     float *ens_vmask = nullptr, *ens_boxes4 = nullptr, *ens_logits = nullptr, *ens_probs = nullptr, *ens_tok = nullptr;
     // second zk member: pairs whose query the rewrite changed (flags, per-wave offsets / lists / counts, compacted feeds and outputs)
     int *ens_diff = nullptr, *ens_doff = nullptr, *ens_dlist = nullptr, *ens_dcount = nullptr;
     int32_t *ens_cq = nullptr, *ens_clen = nullptr, *ens_cnb = nullptr; int64_t* ens_clab = nullptr;
-    float *ens_ctok = nullptr, *ens_clog = nullptr, *ens_cprob = nullptr; int64_t ens_cpairs = 0;
-    // mms_score_ensemble_cascade: first-stage column, kept list, status and the selection workspace (sized for cas_pairs); the gathered batch of the second stage (cas_g_pairs)
-    std::vector<void*> cas_allocs, cas_g_allocs;
-    int64_t cas_pairs = 0, cas_g_pairs = 0;
+    float *ens_ctok = nullptr, *ens_clog = nullptr, *ens_cprob = nullptr;
+    // mms_score_ensemble_cascade: first-stage column, kept list, status and the selection workspace (cas_mem); the gathered batch of the second stage (cas_g_mem)
     float* cas_x = nullptr; int32_t *cas_list = nullptr, *cas_status = nullptr; void* cas_ws = nullptr;
     float *cas_feats = nullptr, *cas_boxes5 = nullptr; int64_t* cas_labels = nullptr;
     int32_t *cas_nb = nullptr, *cas_lab = nullptr, *cas_q = nullptr, *cas_len = nullptr, *cas_q2 = nullptr, *cas_len2 = nullptr, *cas_lxi = nullptr, *cas_lxm = nullptr;
-    Planes ens_featp; int64_t ens_featp_pairs = 0;      // the wave's split box features when the three members run side by side (they may not live in zk's FFN buffer then)
+    Planes ens_featp;      // the wave's split box features when the three members run side by side (they may not live in zk's FFN buffer then)
 
     // ---- gemm timing ----
     bool timing = false;
@@ -190,16 +236,15 @@ int grow_event_pair(mms_handle* h, std::vector<hipEvent_t>& v) {
     return MMS_OK;
 }
 
-int dev_alloc(mms_handle* h, std::vector<void*>& pool, void** out, size_t bytes) {
-    void* p = nullptr;
-    HIP_TRY(h, hipMalloc(&p, bytes ? bytes : 16));
-    pool.push_back(p);
-    *out = p;
-    return MMS_OK;
+int DevPool::fail(mms_handle* h) {
+    const hipError_t e = err;
+    err = hipSuccess;
+    return h->fail(MMS_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
-void free_pool(std::vector<void*>& pool) {
-    for (void* p : pool) (void)hipFree(p);
-    pool.clear();
+int DevPool::done(mms_handle* h, int64_t n) {
+    if (!ok()) { const int rc = fail(h); clear(); return rc; }
+    cap = n;
+    return MMS_OK;
 }
 
 const HostTensor* find(mms_handle* h, const std::string& name) {
@@ -222,10 +267,10 @@ int need(mms_handle* h, const std::string& name, std::vector<int64_t> shape, con
 }
 
 int upload_f32(mms_handle* h, const float* src, size_t n, float** out) {
-    void* p;
-    if (int rc = dev_alloc(h, h->w_allocs, &p, n * 4)) return rc;
+    float* p = h->w_mem.get<float>((int64_t)n);
+    if (!p) return h->w_mem.fail(h);      // (not done(): mms_finalize clears the weight pool when it fails)
     HIP_TRY(h, hipMemcpy(p, src, n * 4, hipMemcpyHostToDevice));
-    *out = (float*)p;
+    *out = p;
     return MMS_OK;
 }
 int vec(mms_handle* h, const std::string& name, int64_t n, float** out) {
@@ -267,11 +312,11 @@ int upload_mat(mms_handle* h, const std::vector<MatSrc>& srcs, int64_t K, bf16**
             }
         r0 += s.n;
     }
-    void* p;
-    if (int rc = dev_alloc(h, h->w_allocs, &p, buf.size() * 2)) return rc;
+    bf16* p = h->w_mem.get<bf16>((int64_t)buf.size());
+    if (!p) return h->w_mem.fail(h);
     HIP_TRY(h, hipMemcpy(p, buf.data(), buf.size() * 2, hipMemcpyHostToDevice));
-    *out = (bf16*)p;
-    if (with_lo) h->w_planes.push_back({(const bf16*)p, N * K});
+    *out = p;
+    if (with_lo) h->w_planes.push_back({p, N * K});
     return MMS_OK;
 }
 // precision mode 4: e4m3 copy [N][K] of the same sources + one power-of-two scale per output channel (quantised on the device:
@@ -286,21 +331,21 @@ int upload_mat_f8(mms_handle* h, const std::vector<MatSrc>& srcs, int64_t K, uns
             for (int64_t k = 0; k < K; ++k) buf[(size_t)((r0 + n) * K + k)] = s.in_out ? s.p[k * s.n + n] : s.p[n * K + k];
         r0 += s.n;
     }
-    float* tmp = nullptr;
-    HIP_TRY(h, hipMalloc((void**)&tmp, buf.size() * 4));
+    DevPool scratch;      // the fp32 source, until this function returns
+    float* tmp = scratch.get<float>((int64_t)buf.size());
+    if (!tmp) return scratch.fail(h);
     hipError_t e = hipMemcpy(tmp, buf.data(), buf.size() * 4, hipMemcpyHostToDevice);
-    void *q = nullptr, *sc = nullptr;
+    unsigned char *q = nullptr, *sc = nullptr;
     int rc = e == hipSuccess ? MMS_OK : h->fail(MMS_ERR_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    if (!rc) rc = dev_alloc(h, h->w_allocs, &q, (size_t)(N * K));
+    if (!rc && !(q = h->w_mem.get<unsigned char>(N * K))) rc = h->w_mem.fail(h);
     if (!rc && (N % 64 || K % 128)) rc = h->fail(MMS_ERR_WEIGHT, "fp8 GEMM weight matrix must have N % 64 == 0 and K % 128 == 0");
-    if (!rc) rc = dev_alloc(h, h->w_allocs, &sc, (size_t)N);
+    if (!rc && !(sc = h->w_mem.get<unsigned char>(N))) rc = h->w_mem.fail(h);      // (N e8m0 bytes, read as packed words)
     if (!rc) {
-        launch_quant_rows_f8(tmp, (unsigned char*)q, nullptr, (unsigned*)sc, (int)N, (int)K, 0);
+        launch_quant_rows_f8(tmp, q, nullptr, (unsigned*)sc, (int)N, (int)K, 0);
         e = hipDeviceSynchronize();
         if (e != hipSuccess) rc = h->fail(MMS_ERR_HIP, std::string("quantise weights: ") + hipGetErrorString(e));
     }
-    (void)hipFree(tmp);
-    *out = (unsigned char*)q; *scale = (unsigned*)sc;
+    *out = q; *scale = (unsigned*)sc;
     return rc;
 }
 int mat_f8(mms_handle* h, const std::string& name, int64_t N, int64_t K, bool in_out, unsigned char** out, unsigned** scale) {
@@ -482,15 +527,14 @@ int finalize_lxmert(mms_handle* h) {
 // ------------------------------------------------------------------------------------------------
 // workspace
 // ------------------------------------------------------------------------------------------------
-int alloc_planes(mms_handle* h, std::vector<void*>& pool, Planes* p, int64_t elems) {
-    void* q;
-    if (int rc = dev_alloc(h, pool, &q, (size_t)elems * 2 * 2)) return rc;
-    p->hi = (bf16*)q;
-    p->lo = p->hi + MMS_PLANE_LO;      // hl32: one buffer of 2 * elems, 32-element blocks of hi and lo alternating (common.h)
-    return MMS_OK;
+int ensure_kparts(mms_handle* h, int64_t floats) {      // (of the lane that is being enqueued)
+    DevPool& mem = h->lane ? h->kparts_side_mem : h->kparts_mem;
+    float*& buf = h->lane ? h->kparts_side : h->kparts;
+    if (floats <= mem.cap) return MMS_OK;
+    mem.clear();
+    buf = mem.get<float>(floats);
+    return mem.done(h, floats);
 }
-
-int ensure_kparts(mms_handle* h, int64_t floats);
 int64_t kparts_need(const mms_handle* h, int64_t pairs, int64_t rows);
 int64_t kparts_side_need(const mms_handle* h, int64_t pairs);
 // the lane-private buffers of the chain that is being enqueued (mms_handle::lane)
@@ -517,11 +561,11 @@ bool lane_query_stage() {
 }
 
 int ensure_workspace(mms_handle* h, int64_t pairs) {
-    if (pairs <= h->ws_pairs) return MMS_OK;
-    free_pool(h->ws_allocs);
-    h->ws_pairs = 0;
+    DevPool& ws = h->ws_mem;
+    if (pairs <= ws.cap) return MMS_OK;
+    ws.clear();
+    h->ens_tok_mem.clear();      // (sized by the workspace's pairs: ensure_ens_tok)
     h->ens_tok = nullptr;
-    h->x.f8 = h->y.f8 = h->ctx.f8 = h->mid.f8 = nullptr;
     const mms_config& c = h->cfg;
     const int64_t T = c.text_len;
     int64_t rows, mid_rows;
@@ -536,92 +580,65 @@ int ensure_workspace(mms_handle* h, int64_t pairs) {
     int64_t mid_elems = mid_rows * c.inter;
     const int64_t feat_elems = pairs * MMS_NBOX * MMS_FEAT;
     if (mid_elems < feat_elems) mid_elems = feat_elems;
-    void* p;
-    if (int rc = alloc_planes(h, h->ws_allocs, &h->x, rows * H)) return rc;
-    if (int rc = alloc_planes(h, h->ws_allocs, &h->ctx, rows * H)) return rc;
-    if (int rc = alloc_planes(h, h->ws_allocs, &h->y, rows * H)) return rc;
-    if (int rc = alloc_planes(h, h->ws_allocs, &h->mid, mid_elems)) return rc;
+    h->x = ws.planes(rows * H);
+    h->ctx = ws.planes(rows * H);
+    h->y = ws.planes(rows * H);
+    h->mid = ws.planes(mid_elems);
     h->mid_elems = mid_elems;
     if (h->f8) {   // e4m3 copies of the GEMM A operands (x / y: LayerNorm outputs, ctx: attention output, mid: FFN intermediate)
         // + 256 rows: gemm_mx8_kernel fetches whole 256-row panels (rows past the live count are multiplied and discarded, never clamped)
-        if (int rc = dev_alloc(h, h->ws_allocs, &p, (size_t)(rows + 256) * H)) return rc;
-        h->x.f8 = (unsigned char*)p;
-        if (int rc = dev_alloc(h, h->ws_allocs, &p, (size_t)(rows + 256) * H)) return rc;
-        h->y.f8 = (unsigned char*)p;
-        if (int rc = dev_alloc(h, h->ws_allocs, &p, (size_t)(rows + 256) * H)) return rc;
-        h->ctx.f8 = (unsigned char*)p;
-        if (int rc = dev_alloc(h, h->ws_allocs, &p, (size_t)(mid_rows + 256) * c.inter)) return rc;
-        h->mid.f8 = (unsigned char*)p;
+        h->x.f8 = ws.get<unsigned char>((rows + 256) * H);
+        h->y.f8 = ws.get<unsigned char>((rows + 256) * H);
+        h->ctx.f8 = ws.get<unsigned char>((rows + 256) * H);
+        h->mid.f8 = ws.get<unsigned char>((mid_rows + 256) * c.inter);
     }
-    if (int rc = dev_alloc(h, h->ws_allocs, &p, (size_t)rows * 3 * H * 4)) return rc;
-    h->qkv = (float*)p;
-    if (int rc = dev_alloc(h, h->ws_allocs, &p, (size_t)rows * H * 4)) return rc;
-    h->t = (float*)p;
-    if (int rc = dev_alloc(h, h->ws_allocs, &p, (size_t)rows * 4)) return rc;
-    h->key_add = (float*)p;
-    if (int rc = dev_alloc(h, h->ws_allocs, &p, (size_t)rows * 4)) return rc;
-    h->key_add2 = (float*)p;
-    if (int rc = dev_alloc(h, h->ws_allocs, &p, (size_t)pairs * H * 4)) return rc;
-    h->pooled = (float*)p;
-    if (int rc = dev_alloc(h, h->ws_allocs, &p, (size_t)pairs * 2 * H * 4)) return rc;
-    h->hbuf = (float*)p;
+    h->qkv = ws.get<float>(rows * 3 * H);
+    h->t = ws.get<float>(rows * H);
+    h->key_add = ws.get<float>(rows);
+    h->key_add2 = ws.get<float>(rows);
+    h->pooled = ws.get<float>(pairs * H);
+    h->hbuf = ws.get<float>(pairs * 2 * H);
     for (int s = 0; s < 2; ++s) {
-        if (int rc = dev_alloc(h, h->ws_allocs, &p, (size_t)pairs * 4)) return rc;
-        h->pk_off[s] = (int*)p;
-        if (int rc = dev_alloc(h, h->ws_allocs, &p, (size_t)pairs * 4)) return rc;
-        h->pk_cnt[s] = (int*)p;
-        if (int rc = dev_alloc(h, h->ws_allocs, &p, (size_t)rows * 4)) return rc;
-        h->pk_src[s] = (int*)p;
+        h->pk_off[s] = ws.get<int>(pairs);
+        h->pk_cnt[s] = ws.get<int>(pairs);
+        h->pk_src[s] = ws.get<int>(rows);
     }
-    if (int rc = dev_alloc(h, h->ws_allocs, &p, 16)) return rc;
-    h->pk_rows = (int*)p;
-    for (int s = 0; s < (c.model == MMS_MODEL_LXMERT ? 4 : 2); ++s) {      // a sub-tile holds at least one pair
-        if (int rc = dev_alloc(h, h->ws_allocs, &p, (size_t)(pairs + 2) * sizeof(int4))) return rc;
-        h->qa_sub[s] = (int4*)p;
+    h->pk_rows = ws.get<int>(4);
+    for (int s = 0; s < (c.model == MMS_MODEL_LXMERT ? 4 : 2); ++s) h->qa_sub[s] = ws.get<int4>(pairs + 2);      // a sub-tile holds at least one pair
+    for (int s = 0; s < (c.model == MMS_MODEL_LXMERT ? 3 : 1); ++s) h->qa_rec[s] = ws.get<int>(pairs + 2);
+    h->qa_jump = ws.get<int>(qkv_plan_scratch_ints((int)pairs));
+    h->qa_nsub = ws.get<int>(4);
+    const int64_t ln_floats = (rows + 256) * 3 * 2 * 2;      // 8 bytes per (row, column tile, granule)
+    h->ln_stats = ws.get<float>(ln_floats);
+    if (ws.ok()) HIP_TRY(h, hipMemset(h->ln_stats, 0, (size_t)ln_floats * 4));
+    h->ln_ctl = ws.get<int>(mms_handle::LN_SLOTS * 2);
+    if (ws.ok()) {      // whichever call sizes the workspace: the partials of both lanes come with it, never inside a scoring call
+        if (int rc = ensure_kparts(h, kparts_need(h, pairs, rows))) return rc;
+        if (c.model == MMS_MODEL_LXMERT && lane_rows() > 0) {
+            h->lane = 1;
+            const int rc = ensure_kparts(h, kparts_side_need(h, pairs));
+            h->lane = 0;
+            if (rc) return rc;
+        }
     }
-    for (int s = 0; s < (c.model == MMS_MODEL_LXMERT ? 3 : 1); ++s) {
-        if (int rc = dev_alloc(h, h->ws_allocs, &p, (size_t)(pairs + 2) * 4)) return rc;
-        h->qa_rec[s] = (int*)p;
-    }
-    if (int rc = dev_alloc(h, h->ws_allocs, &p, (size_t)qkv_plan_scratch_ints((int)pairs) * 4)) return rc;
-    h->qa_jump = (int*)p;
-    if (int rc = dev_alloc(h, h->ws_allocs, &p, 16)) return rc;
-    h->qa_nsub = (int*)p;
-    if (int rc = dev_alloc(h, h->ws_allocs, &p, (size_t)(rows + 256) * 3 * 2 * 8)) return rc;
-    h->ln_stats = (float*)p;
-    HIP_TRY(h, hipMemset(p, 0, (size_t)(rows + 256) * 3 * 2 * 8));
-    if (int rc = dev_alloc(h, h->ws_allocs, &p, (size_t)mms_handle::LN_SLOTS * 2 * 4)) return rc;
-    h->ln_ctl = (int*)p;
-    if (int rc = ensure_kparts(h, kparts_need(h, pairs, rows))) return rc;
-    if (c.model == MMS_MODEL_LXMERT && lane_rows() > 0) {      // whichever call sizes the workspace: the side lane's partials come with it, never inside a scoring call
-        h->lane = 1;
-        const int rc = ensure_kparts(h, kparts_side_need(h, pairs));
-        h->lane = 0;
-        if (rc) return rc;
-    }
-    h->ws_pairs = pairs;
-    return MMS_OK;
+    return ws.done(h, pairs);
 }
 
 constexpr int64_t LAB_CHUNK = 2048;  // unique label texts encoded per GEMM wave (bounds the im2col buffer)
 
 int ensure_label_ws(mms_handle* h, int64_t U) {
-    if (U > h->lab_feat_cap || h->lab_cap == 0) {
-        free_pool(h->lab_allocs);
-        h->lab_cap = 0;
-        const int64_t cap = U < LAB_CHUNK ? U : LAB_CHUNK;
-        const int64_t kdim = h->cfg.model == MMS_MODEL_ZK ? (int64_t)MMS_LABEL_LEN * H : H;
-        const int64_t rows = h->cfg.model == MMS_MODEL_ZK ? cap * MMS_LABEL_LEN : cap;
-        void* p;
-        if (int rc = alloc_planes(h, h->lab_allocs, &h->lab_planes, rows * kdim)) return rc;
-        if (int rc = dev_alloc(h, h->lab_allocs, &p, (size_t)rows * H * 4)) return rc;
-        h->lab_f32 = (float*)p;
-        if (int rc = dev_alloc(h, h->lab_allocs, &p, (size_t)U * H * 4)) return rc;
-        h->lab_feat = (float*)p;
-        h->lab_cap = cap;
-        h->lab_feat_cap = U;
-    }
-    return MMS_OK;
+    DevPool& lab = h->lab_mem;
+    if (U <= lab.cap && h->lab_cap != 0) return MMS_OK;
+    lab.clear();
+    h->lab_cap = 0;
+    const int64_t cap = U < LAB_CHUNK ? U : LAB_CHUNK;
+    const int64_t kdim = h->cfg.model == MMS_MODEL_ZK ? (int64_t)MMS_LABEL_LEN * H : H;
+    const int64_t rows = h->cfg.model == MMS_MODEL_ZK ? cap * MMS_LABEL_LEN : cap;
+    h->lab_planes = lab.planes(rows * kdim);
+    h->lab_f32 = lab.get<float>(rows * H);
+    h->lab_feat = lab.get<float>(U * H);
+    if (lab.ok()) h->lab_cap = cap;
+    return lab.done(h, U);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -634,7 +651,6 @@ struct GemmOut {
     RowMap cmap{0, 0, 0};
 };
 
-int ensure_kparts(mms_handle* h, int64_t floats);
 // Launches of at most SKINNY_ROWS padded rows in precision modes 2 and 3 (the reference's zk call size: 1 pair = 30 token rows; up to 4 zk / 3 lds / 6 lxmert pairs,
 // and the box-row projections of up to 12 pairs): gemm_skinny.hip -- one workgroup per 16 output columns, no LDS staging; K split over the workgroup's waves
 // (wide projections: ONE launch where the split-K tile route needs two) or, where a LayerNorm / reduce launch follows anyway, over single-wave workgroups
@@ -897,16 +913,6 @@ int splitk_for(const mms_handle* h, int64_t M, int K) {
     }
 #endif
     return K % (64 * S) == 0 ? S : 1;
-}
-int ensure_kparts(mms_handle* h, int64_t floats) {      // (of the lane that is being enqueued)
-    float*& buf = h->lane ? h->kparts_side : h->kparts;
-    int64_t& have = h->lane ? h->kparts_side_floats : h->kparts_floats;
-    if (floats <= have) return MMS_OK;
-    if (buf) { (void)hipFree(buf); buf = nullptr; have = 0; }      // (hipFree waits for the work that may still read it)
-    void* p = nullptr;
-    HIP_TRY(h, hipMalloc(&p, (size_t)floats * 4));
-    buf = (float*)p; have = floats;
-    return MMS_OK;
 }
 // Partials of every split-K launch a workspace of `pairs` pairs can issue (sized here, with the workspace, so that a scoring call on a warmed-up
 // handle never allocates; a 1-pair handle holds ~2 MB instead of a fixed 200 MB): the N = 768 projections of launches below SPLITK_ROWS token rows (8 slices x rows x 768), the
@@ -1174,29 +1180,20 @@ struct DeviceScope {
 // label-text tuples: dense [B*10, 8] ids -> distinct tuples + per-row index (batchops.hip)
 // ------------------------------------------------------------------------------------------------
 int ensure_dedup_ws(mms_handle* h, int64_t rows) {
-    if (rows <= h->dd_rows) return MMS_OK;
-    free_pool(h->dd_allocs);
-    h->dd_rows = 0;
+    DevPool& dd = h->dd_mem;
+    if (rows <= dd.cap) return MMS_OK;
+    dd.clear();
     int cap = 1024;
     while (cap < 2 * rows) cap <<= 1;
-    void* p;
-    if (int rc = dev_alloc(h, h->dd_allocs, &p, (size_t)cap * 4)) return rc;
-    h->dd_slots = (int*)p;
-    if (int rc = dev_alloc(h, h->dd_allocs, &p, (size_t)rows * 4)) return rc;
-    h->dd_rep = (int*)p;
-    if (int rc = dev_alloc(h, h->dd_allocs, &p, (size_t)rows * 4)) return rc;
-    h->dd_uid = (int*)p;
-    if (int rc = dev_alloc(h, h->dd_allocs, &p, (size_t)rows * 4)) return rc;
-    h->dd_index = (int*)p;
-    if (int rc = dev_alloc(h, h->dd_allocs, &p, 16)) return rc;
-    h->dd_counter = (int*)p;
-    if (int rc = dev_alloc(h, h->dd_allocs, &p, (size_t)rows * MMS_LABEL_LEN * 4)) return rc;
-    h->dd_uniq32 = (int32_t*)p;
-    if (int rc = dev_alloc(h, h->dd_allocs, &p, (size_t)rows * MMS_LABEL_LEN * 8)) return rc;
-    h->dd_uniq64 = (int64_t*)p;
+    h->dd_slots = dd.get<int>(cap);
+    h->dd_rep = dd.get<int>(rows);
+    h->dd_uid = dd.get<int>(rows);
+    h->dd_index = dd.get<int>(rows);
+    h->dd_counter = dd.get<int>(4);
+    h->dd_uniq32 = dd.get<int32_t>(rows * MMS_LABEL_LEN);
+    h->dd_uniq64 = dd.get<int64_t>(rows * MMS_LABEL_LEN);
     h->dd_cap = cap;
-    h->dd_rows = rows;
-    return MMS_OK;
+    return dd.done(h, rows);
 }
 
 // Finds the distinct tuples of ids[rows][8] (T = int32_t: zk feed, int64_t: lxmert feed): h->dd_uniq32 / dd_uniq64 hold them,
@@ -1438,29 +1435,55 @@ struct LaneGuard {
     }
 };
 
+// the distinct-query stage's buffers: tables that scale with the call (B pairs), the store planes (dense [Q, T] rows of the Q distinct queries; they live outside
+// the chunk workspace) and the gathered inputs of one sub-batch of cs queries
+int ensure_lq_ws(mms_handle* h, int64_t B) {
+    DevPool& lq = h->lq_mem;
+    if (B <= lq.cap) return MMS_OK;
+    lq.clear();
+    h->lq_sub_mem.clear();
+    h->lq_store_mem.cap = 0;      // (re-made, and only then freed, by the next call that shares queries)
+    int cap = 1024;
+    while (cap < 2 * B) cap <<= 1;
+    h->lq_slots = lq.get<int>((int64_t)cap * 2);     // hash table + per-slot smallest row (launch_query_dedup)
+    h->lq_rep = lq.get<int>(B);
+    h->lq_uid = lq.get<int>(B);
+    h->lq_rows_of = lq.get<int>(B);
+    h->lq_index = lq.get<int>(B);
+    h->lq_counter = lq.get<int>(4);
+    h->lq_cap = cap;
+    return lq.done(h, B);
+}
+int ensure_lq_store(mms_handle* h, int64_t Q, int T) {
+    DevPool& store = h->lq_store_mem;
+    if (Q <= store.cap) return MMS_OK;
+    store.clear();
+    h->lq_store = store.planes(Q * T * H);
+    return store.done(h, Q);
+}
+int ensure_lq_sub(mms_handle* h, int cs, int T) {
+    DevPool& sub = h->lq_sub_mem;
+    if (cs <= sub.cap) return MMS_OK;
+    sub.clear();
+    h->lq_ids = sub.get<int64_t>((int64_t)cs * T);
+    h->lq_mask = sub.get<int64_t>((int64_t)cs * T);
+    h->lq_pk_off = sub.get<int>(cs);
+    h->lq_pk_cnt = sub.get<int>(cs);
+    h->lq_pk_src = sub.get<int>((int64_t)cs * T);
+    h->lq_key_add = sub.get<float>((int64_t)cs * T);
+    h->lq_qa_sub = sub.get<int4>(cs + 2);
+    h->lq_qa_rec = sub.get<int>(cs + 2);
+    h->lq_qa_jump = sub.get<int>(qkv_plan_scratch_ints(cs));
+    return sub.done(h, cs);
+}
+
 int lx_query_stage(mms_handle* h, hipStream_t st, const mms_lxmert_batch* b, int64_t B, int cs) {
     const mms_config& c = h->cfg;
     h->lq_active = false;
     h->lq_join_pending = false;
     if (!c.pack_tokens || c.stop_after >= 0 || c.layers <= 0 || B < 2) return MMS_OK;
     const int T = c.text_len;
-    if (B > h->lq_pairs) {
-        free_pool(h->lq_allocs);
-        free_pool(h->lq_sub_allocs);
-        h->lq_pairs = 0; h->lq_store_q = 0; h->lq_sub = 0;
-        int cap = 1024;
-        while (cap < 2 * B) cap <<= 1;
-        void* p;
-        auto get = [&](size_t bytes, void** out) { int rc = dev_alloc(h, h->lq_allocs, &p, bytes); *out = p; return rc; };
-        if (int rc = get((size_t)cap * 2 * 4, (void**)&h->lq_slots)) return rc;      // hash table + per-slot smallest row (launch_query_dedup)
-        if (int rc = get((size_t)B * 4, (void**)&h->lq_rep)) return rc;
-        if (int rc = get((size_t)B * 4, (void**)&h->lq_uid)) return rc;
-        if (int rc = get((size_t)B * 4, (void**)&h->lq_rows_of)) return rc;
-        if (int rc = get((size_t)B * 4, (void**)&h->lq_index)) return rc;
-        if (int rc = get(16, (void**)&h->lq_counter)) return rc;
-        h->lq_cap = cap;
-        h->lq_pairs = B;
-    }
+    if (int rc = ensure_lq_ws(h, B)) return rc;
     launch_query_dedup(b->input_ids, b->input_mask, T, (int)B, h->lq_slots, h->lq_cap, h->lq_rep, h->lq_uid, h->lq_counter, h->lq_rows_of,
                        h->lq_index, st);
     int nq = 0;
@@ -1468,36 +1491,8 @@ int lx_query_stage(mms_handle* h, hipStream_t st, const mms_lxmert_batch* b, int
     HIP_TRY(h, hipStreamSynchronize(st));
     const int64_t Q = nq;
     if (Q * 2 > B) return MMS_OK;                       // little sharing: not worth the extra copy
-    if (Q > h->lq_store_q) {                            // store planes (dense [Q, T] rows) live outside the chunk workspace
-        if (h->lq_store.hi) { (void)hipFree(h->lq_store.hi); h->lq_store.hi = nullptr; }
-        void* p = nullptr;
-        HIP_TRY(h, hipMalloc(&p, (size_t)Q * T * H * 4));
-        h->lq_store.hi = (bf16*)p; h->lq_store.lo = h->lq_store.hi + MMS_PLANE_LO;
-        h->lq_store_q = Q;
-    }
-    if (cs > h->lq_sub) {                               // gathered inputs of one sub-batch of distinct queries
-        void* p;
-        free_pool(h->lq_sub_allocs);                    // hipFree waits for the work that may still read the old pair
-        if (int rc = dev_alloc(h, h->lq_sub_allocs, &p, (size_t)cs * T * 8)) return rc;
-        h->lq_ids = (int64_t*)p;
-        if (int rc = dev_alloc(h, h->lq_sub_allocs, &p, (size_t)cs * T * 8)) return rc;
-        h->lq_mask = (int64_t*)p;
-        if (int rc = dev_alloc(h, h->lq_sub_allocs, &p, (size_t)cs * 4)) return rc;
-        h->lq_pk_off = (int*)p;
-        if (int rc = dev_alloc(h, h->lq_sub_allocs, &p, (size_t)cs * 4)) return rc;
-        h->lq_pk_cnt = (int*)p;
-        if (int rc = dev_alloc(h, h->lq_sub_allocs, &p, (size_t)cs * T * 4)) return rc;
-        h->lq_pk_src = (int*)p;
-        if (int rc = dev_alloc(h, h->lq_sub_allocs, &p, (size_t)cs * T * 4)) return rc;
-        h->lq_key_add = (float*)p;
-        if (int rc = dev_alloc(h, h->lq_sub_allocs, &p, (size_t)(cs + 2) * sizeof(int4))) return rc;
-        h->lq_qa_sub = (int4*)p;
-        if (int rc = dev_alloc(h, h->lq_sub_allocs, &p, (size_t)(cs + 2) * 4)) return rc;
-        h->lq_qa_rec = (int*)p;
-        if (int rc = dev_alloc(h, h->lq_sub_allocs, &p, (size_t)qkv_plan_scratch_ints(cs) * 4)) return rc;
-        h->lq_qa_jump = (int*)p;
-        h->lq_sub = cs;
-    }
+    if (int rc = ensure_lq_store(h, Q, T)) return rc;
+    if (int rc = ensure_lq_sub(h, cs, T)) return rc;
     // One chunk, one sub-batch, a small call (two lanes): the stage runs on the side lane beside the chunk's box-stream prologue and r_layers (lx_chunk joins
     // before it copies the language rows out of lq_store).  The stage's rows [0, Q T) of x / y / ctx / qkv / t lie inside the chunk's language rows, which the
     // chunk does not touch before the join; its packed plan, its sub-tile table and the plan scratch are its own.
@@ -2065,26 +2060,12 @@ int mms_create(const mms_config* cfg, mms_handle** out) {
 void mms_destroy(mms_handle* h) {
     if (!h) return;
     DeviceScope dev(h->cfg.device);
-    free_pool(h->w_allocs);
-    free_pool(h->ws_allocs);
-    free_pool(h->lab_allocs);
-    free_pool(h->dd_allocs);
-    free_pool(h->ens_allocs);
-    free_pool(h->ens_c_allocs);
-    free_pool(h->cas_allocs);
-    free_pool(h->cas_g_allocs);
-    free_pool(h->lq_allocs);
-    free_pool(h->lq_sub_allocs);
-    if (h->lq_store.hi) (void)hipFree(h->lq_store.hi);
-    if (h->kparts) (void)hipFree(h->kparts);
-    if (h->kparts_side) (void)hipFree(h->kparts_side);
-    if (h->ens_featp.hi) (void)hipFree(h->ens_featp.hi);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     if (h->side) (void)hipStreamDestroy(h->side);
     for (auto e : h->ev) (void)hipEventDestroy(e);
     for (auto e : h->ev_fused) (void)hipEventDestroy(e);
-    delete h;
+    delete h;      // (frees the device memory: every buffer belongs to a DevPool member)
 }
 
 int mms_load_weight(mms_handle* h, const char* name, const float* host_data, const int64_t* shape, int32_t rank) {
@@ -2106,7 +2087,7 @@ int mms_finalize(mms_handle* h) {
     DeviceScope dev(h->cfg.device);
     int rc = h->cfg.model == MMS_MODEL_ZK ? finalize_zk(h) : h->cfg.model == MMS_MODEL_LDS ? finalize_lds(h) : finalize_lxmert(h);
     if (rc) {   // leave nothing dangling: a retry (after loading the missing tensor) starts from a clean handle
-        free_pool(h->w_allocs);
+        h->w_mem.clear();
         h->w_planes.clear(); h->flop_counter = nullptr; h->timing = false;
         h->layers.clear(); h->r_layers.clear(); h->x_layers.clear();
         return rc;
@@ -2201,28 +2182,55 @@ int mms_score_lxmert(mms_handle* h, const mms_lxmert_batch* b, float* logits, fl
 
 // ---- the three models on the same pairs in one call (BASELINE.json config 5; merge of code/main.py:59) ----
 static int ensure_ens_ws(mms_handle* z, int64_t B, int T, int TL) {
-    if (B <= z->ens_pairs) return MMS_OK;
-    free_pool(z->ens_allocs);
-    free_pool(z->ens_c_allocs);
-    z->ens_pairs = 0;
-    void* p;
-    auto get = [&](size_t bytes, void** out) { int rc = dev_alloc(z, z->ens_allocs, &p, bytes); *out = p; return rc; };
-    if (int rc = get((size_t)B * (T + MMS_NBOX) * 4, (void**)&z->ens_seg)) return rc;
-    if (int rc = get((size_t)B * T * 8, (void**)&z->ens_ids64)) return rc;
-    if (int rc = get((size_t)B * T * 8, (void**)&z->ens_seg64)) return rc;
-    if (int rc = get((size_t)B * MMS_NBOX * MMS_LABEL_LEN * 8, (void**)&z->ens_lab64)) return rc;
-    if (int rc = get((size_t)B * TL * 8 * 2, (void**)&z->ens_mask64)) return rc;     // lxmert ids, then mask
-    if (int rc = get((size_t)B * MMS_NBOX * 4, (void**)&z->ens_vmask)) return rc;
-    if (int rc = get((size_t)B * MMS_NBOX * 4 * 4, (void**)&z->ens_boxes4)) return rc;
-    if (int rc = get((size_t)B * 2 * 4 * 4, (void**)&z->ens_logits)) return rc;
-    if (int rc = get((size_t)B * 2 * 4 * 4, (void**)&z->ens_probs)) return rc;
-    if (int rc = get((size_t)B * 4, (void**)&z->ens_diff)) return rc;
-    if (int rc = get((size_t)B * 4, (void**)&z->ens_doff)) return rc;
-    if (int rc = get((size_t)B * 4, (void**)&z->ens_dlist)) return rc;
-    if (int rc = get((size_t)(B / 64 + 16) * 4, (void**)&z->ens_dcount)) return rc;
-    z->ens_cpairs = 0;
-    z->ens_pairs = B;
-    return MMS_OK;
+    DevPool& ens = z->ens_mem;
+    if (B <= ens.cap) return MMS_OK;
+    ens.clear();
+    z->ens_c_mem.clear();
+    z->ens_seg = ens.get<int32_t>(B * (T + MMS_NBOX));
+    z->ens_ids64 = ens.get<int64_t>(B * T);
+    z->ens_seg64 = ens.get<int64_t>(B * T);
+    z->ens_lab64 = ens.get<int64_t>(B * MMS_NBOX * MMS_LABEL_LEN);
+    z->ens_mask64 = ens.get<int64_t>(B * TL * 2);     // lxmert ids, then mask
+    z->ens_vmask = ens.get<float>(B * MMS_NBOX);
+    z->ens_boxes4 = ens.get<float>(B * MMS_NBOX * 4);
+    z->ens_logits = ens.get<float>(B * 2 * 4);
+    z->ens_probs = ens.get<float>(B * 2 * 4);
+    z->ens_diff = ens.get<int>(B);
+    z->ens_doff = ens.get<int>(B);
+    z->ens_dlist = ens.get<int>(B);
+    z->ens_dcount = ens.get<int>(B / 64 + 16);
+    return ens.done(z, B);
+}
+// the wave's split box features when the members run side by side (cs pairs per wave)
+static int ensure_ens_featp(mms_handle* z, int cs) {
+    DevPool& mem = z->ens_featp_mem;
+    if (cs <= mem.cap) return MMS_OK;
+    mem.clear();
+    z->ens_featp = mem.planes((int64_t)cs * MMS_NBOX * MMS_FEAT);
+    return mem.done(z, cs);
+}
+// image tokens of a wave survive zk's first encoder pass in a side buffer (the QKV buffer they are built in gets reused): made by the first ensemble call that
+// runs the zk members, sized by the workspace's pairs and cleared when the workspace regrows (ensure_workspace)
+static int ensure_ens_tok(mms_handle* z) {
+    DevPool& mem = z->ens_tok_mem;
+    if (mem.cap) return MMS_OK;
+    mem.clear();
+    z->ens_tok = mem.get<float>(z->ws_mem.cap * MMS_NBOX * H);
+    return mem.done(z, z->ws_mem.cap);
+}
+// second zk member: the compacted feeds and outputs of the pairs whose query the rewrite changed (the largest count of a wave)
+static int ensure_ens_changed(mms_handle* z, int64_t need, int T) {
+    DevPool& mem = z->ens_c_mem;
+    if (need <= mem.cap) return MMS_OK;
+    mem.clear();
+    z->ens_cq = mem.get<int32_t>(need * T);
+    z->ens_clen = mem.get<int32_t>(need);
+    z->ens_cnb = mem.get<int32_t>(need);
+    z->ens_clab = mem.get<int64_t>(need);
+    z->ens_ctok = mem.get<float>(need * MMS_NBOX * H);
+    z->ens_clog = mem.get<float>(need * 2);
+    z->ens_cprob = mem.get<float>(need * 2);
+    return mem.done(z, need);
 }
 
 // the argument checks of the two ensemble entry points (B == 0 passes: the caller returns before anything is read)
@@ -2313,13 +2321,7 @@ static int ens_run(mms_handle* z, mms_handle* l, mms_handle* x, const mms_ensemb
     if (ens_lanes) {
         if (int rc = lanes_init(z)) return rc;
         if (int rc = lanes_init(l)) return z->fail(rc, "lds handle: " + l->err);
-        if (cs > z->ens_featp_pairs) {
-            if (z->ens_featp.hi) { (void)hipFree(z->ens_featp.hi); z->ens_featp.hi = nullptr; z->ens_featp_pairs = 0; }
-            void* q = nullptr;
-            HIP_TRY(z, hipMalloc(&q, (size_t)cs * MMS_NBOX * MMS_FEAT * 4));
-            z->ens_featp.hi = (bf16*)q; z->ens_featp.lo = z->ens_featp.hi + MMS_PLANE_LO;
-            z->ens_featp_pairs = cs;
-        }
+        if (int rc = ensure_ens_featp(z, cs)) return rc;
     }
     // two lanes inside the lxmert member's chunks as in mms_score_lxmert; its distinct-query stage goes to the side lane only in the small-wave regime above: beside
     // the other members' big launches with fused LayerNorm epilogues it would break those (gemm_ln)
@@ -2331,12 +2333,7 @@ static int ens_run(mms_handle* z, mms_handle* l, mms_handle* x, const mms_ensemb
     float* lg[4]; float* pr[4];
     for (int k = 0; k < 4; ++k) { lg[k] = z->ens_logits + (int64_t)k * B * 2; pr[k] = z->ens_probs + (int64_t)k * B * 2; }
 
-    // image tokens of a wave survive zk's first encoder pass in a side buffer (the QKV buffer they are built in gets reused)
-    if (do_z && !z->ens_tok) {
-        void* p;
-        if (int rc = dev_alloc(z, z->ws_allocs, &p, (size_t)z->ws_pairs * MMS_NBOX * H * 4)) return rc;   // lives and dies with the workspace
-        z->ens_tok = (float*)p;
-    }
+    if (do_z) if (int rc = ensure_ens_tok(z)) return rc;
     // second zk member: the rewrite (load_data_v4.py:153-154) touches only queries that contain the phrase; every other pair's second
     // forward would repeat the first one bit for bit, so only the changed pairs are encoded again (per launch wave: flags -> scan ->
     // compact list; the per-wave counts come back in one small read)
@@ -2353,30 +2350,9 @@ static int ens_run(mms_handle* z, mms_handle* l, mms_handle* x, const mms_ensemb
         HIP_TRY(z, hipMemcpyAsync(changed.data(), z->ens_dcount, (size_t)n_waves * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(z, hipStreamSynchronize(st));
     }
-    {
-        int64_t need = 0;
-        for (int v : changed) need = v > need ? v : need;
-        if (need > z->ens_cpairs) {
-            void* p;
-            free_pool(z->ens_c_allocs);
-            const int S = T + MMS_NBOX; (void)S;
-            if (int rc = dev_alloc(z, z->ens_c_allocs, &p, (size_t)need * T * 4)) return rc;
-            z->ens_cq = (int32_t*)p;
-            if (int rc = dev_alloc(z, z->ens_c_allocs, &p, (size_t)need * 4)) return rc;
-            z->ens_clen = (int32_t*)p;
-            if (int rc = dev_alloc(z, z->ens_c_allocs, &p, (size_t)need * 4)) return rc;
-            z->ens_cnb = (int32_t*)p;
-            if (int rc = dev_alloc(z, z->ens_c_allocs, &p, (size_t)need * 8)) return rc;
-            z->ens_clab = (int64_t*)p;
-            if (int rc = dev_alloc(z, z->ens_c_allocs, &p, (size_t)need * MMS_NBOX * H * 4)) return rc;
-            z->ens_ctok = (float*)p;
-            if (int rc = dev_alloc(z, z->ens_c_allocs, &p, (size_t)need * 2 * 4)) return rc;
-            z->ens_clog = (float*)p;
-            if (int rc = dev_alloc(z, z->ens_c_allocs, &p, (size_t)need * 2 * 4)) return rc;
-            z->ens_cprob = (float*)p;
-            z->ens_cpairs = need;
-        }
-    }
+    int64_t most_changed = 0;
+    for (int v : changed) most_changed = v > most_changed ? v : most_changed;
+    if (int rc = ensure_ens_changed(z, most_changed, T)) return rc;
     for (int64_t p0 = 0; p0 < B; p0 += cs) {
         const int64_t n = (B - p0) < cs ? (B - p0) : cs;
         const int64_t NB = n * MMS_NBOX;
@@ -2455,37 +2431,31 @@ int mms_cascade_select(const int64_t* group_ids, const float* score_f32, int64_t
 
 // buffers of the cascade that scale with the call (B pairs) and with the second stage (n_kept pairs): both grow on demand and are kept
 static int ensure_cas_ws(mms_handle* z, int64_t B) {
-    if (B <= z->cas_pairs) return MMS_OK;
-    free_pool(z->cas_allocs);
-    z->cas_pairs = 0;
-    void* p;
-    auto get = [&](size_t bytes, void** out) { int rc = dev_alloc(z, z->cas_allocs, &p, bytes); *out = p; return rc; };
-    if (int rc = get((size_t)B * 4, (void**)&z->cas_x)) return rc;
-    if (int rc = get((size_t)B * 4, (void**)&z->cas_list)) return rc;
-    if (int rc = get(16, (void**)&z->cas_status)) return rc;
-    if (int rc = get((size_t)cascade_workspace_bytes(B), &z->cas_ws)) return rc;
-    z->cas_pairs = B;
-    return MMS_OK;
+    DevPool& cas = z->cas_mem;
+    if (B <= cas.cap) return MMS_OK;
+    cas.clear();
+    z->cas_x = cas.get<float>(B);
+    z->cas_list = cas.get<int32_t>(B);
+    z->cas_status = cas.get<int32_t>(4);
+    z->cas_ws = cas.get<unsigned char>(cascade_workspace_bytes(B));
+    return cas.done(z, B);
 }
 static int ensure_cas_gather(mms_handle* z, int64_t n, int T, int TL) {
-    if (n <= z->cas_g_pairs) return MMS_OK;
-    free_pool(z->cas_g_allocs);
-    z->cas_g_pairs = 0;
-    void* p;
-    auto get = [&](size_t bytes, void** out) { int rc = dev_alloc(z, z->cas_g_allocs, &p, bytes); *out = p; return rc; };
-    if (int rc = get((size_t)n * MMS_NBOX * MMS_FEAT * 4, (void**)&z->cas_feats)) return rc;
-    if (int rc = get((size_t)n * MMS_NBOX * 5 * 4, (void**)&z->cas_boxes5)) return rc;
-    if (int rc = get((size_t)n * 4, (void**)&z->cas_nb)) return rc;
-    if (int rc = get((size_t)n * MMS_NBOX * MMS_LABEL_LEN * 4, (void**)&z->cas_lab)) return rc;
-    if (int rc = get((size_t)n * T * 4, (void**)&z->cas_q)) return rc;
-    if (int rc = get((size_t)n * 4, (void**)&z->cas_len)) return rc;
-    if (int rc = get((size_t)n * T * 4, (void**)&z->cas_q2)) return rc;
-    if (int rc = get((size_t)n * 4, (void**)&z->cas_len2)) return rc;
-    if (int rc = get((size_t)n * 8, (void**)&z->cas_labels)) return rc;
-    if (int rc = get((size_t)n * TL * 4, (void**)&z->cas_lxi)) return rc;
-    if (int rc = get((size_t)n * TL * 4, (void**)&z->cas_lxm)) return rc;
-    z->cas_g_pairs = n;
-    return MMS_OK;
+    DevPool& g = z->cas_g_mem;
+    if (n <= g.cap) return MMS_OK;
+    g.clear();
+    z->cas_feats = g.get<float>(n * MMS_NBOX * MMS_FEAT);
+    z->cas_boxes5 = g.get<float>(n * MMS_NBOX * 5);
+    z->cas_nb = g.get<int32_t>(n);
+    z->cas_lab = g.get<int32_t>(n * MMS_NBOX * MMS_LABEL_LEN);
+    z->cas_q = g.get<int32_t>(n * T);
+    z->cas_len = g.get<int32_t>(n);
+    z->cas_q2 = g.get<int32_t>(n * T);
+    z->cas_len2 = g.get<int32_t>(n);
+    z->cas_labels = g.get<int64_t>(n);
+    z->cas_lxi = g.get<int32_t>(n * TL);
+    z->cas_lxm = g.get<int32_t>(n * TL);
+    return g.done(z, n);
 }
 
 int mms_score_ensemble_cascade(mms_handle* z, mms_handle* l, mms_handle* x, const mms_ensemble_batch* b, const int64_t* group_ids, int32_t keep,
@@ -2540,10 +2510,9 @@ int mms_gemm_timing(mms_handle* h, int32_t enable, int32_t reset, double* ms_out
     if (!h) return MMS_ERR_ARG;
     DeviceScope dev(h->cfg.device);
     if (!h->flop_counter) {
-        void* p;
-        if (int rc = dev_alloc(h, h->w_allocs, &p, 32)) return rc;      // [0]: GEMM launches, [1]: fused QKV + attention launches, [2]: LayerNorm-fused GEMM launches, [3]: side-lane launches (untimed)
-        h->flop_counter = (unsigned long long*)p;
-        HIP_TRY(h, hipMemset(p, 0, 32));
+        h->flop_counter = h->w_mem.get<unsigned long long>(4);      // [0]: GEMM launches, [1]: fused QKV + attention launches, [2]: LayerNorm-fused GEMM launches, [3]: side-lane launches (untimed)
+        if (!h->flop_counter) return h->w_mem.fail(h);      // (not done(): the weights stay)
+        HIP_TRY(h, hipMemset(h->flop_counter, 0, 32));
     }
     if (ms_out || launches_out || flops_out) {
         double ms = 0;
@@ -2619,15 +2588,15 @@ int mms_side_lane_flops(mms_handle* h, double* flops_out) {
 
 int mms_debug_read_x(mms_handle* h, float* dst_dev, int64_t rows, void* stream) {
     if (!h || !dst_dev) return MMS_ERR_ARG;
-    if (!h->ws_pairs) return h->fail(MMS_ERR_STATE, "no forward has run yet");
-    if (rows < 0 || rows > h->ws_pairs * h->x_rows) return h->fail(MMS_ERR_ARG, "rows exceeds the workspace");
+    if (!h->ws_mem.cap) return h->fail(MMS_ERR_STATE, "no forward has run yet");
+    if (rows < 0 || rows > h->ws_mem.cap * h->x_rows) return h->fail(MMS_ERR_ARG, "rows exceeds the workspace");
     launch_planes_to_f32(h->x.hi, h->x.lo, dst_dev, rows * H, (hipStream_t)stream);
     return post_launch(h);
 }
 
 int64_t mms_dbg_counter(mms_handle* h, int32_t which) {
     if (!h) return -1;
-    return which == 0 ? h->fused_attn_launches : which == 1 ? h->ln_fused_launches : which == 2 ? h->splitk_launches : which == 3 ? h->skinny_launches : which == 4 ? h->lane_forks : -1;
+    return which == 0 ? h->fused_attn_launches : which == 1 ? h->ln_fused_launches : which == 2 ? h->splitk_launches : which == 3 ? h->skinny_launches : which == 4 ? h->lane_forks : which == 5 ? (int64_t)h->held() : -1;
 }
 
 }  // extern "C"

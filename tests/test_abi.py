@@ -219,3 +219,19 @@ def test_the_handle_free_hooks_live_in_their_own_file_behind_one_resource_frame(
     assert not re.search(r"^\w[\w\s\*]*\b(?:%s)\s*\(" % moved, api, flags=re.M), "api.hip still defines a handle-free hook"
     for name in sorted(set(re.findall(r"\b(?:%s)\b" % moved, open(os.path.join(ROOT, "include", "mmscore.h")).read()))):
         assert re.search(r"^int %s\(" % name, hooks, flags=re.M), name      # ... and test_hooks.hip defines every one the header declares
+
+
+def test_the_handle_owns_its_device_memory_through_one_pool_type():
+    """csrc/api.hip: device memory is acquired and released by struct DevPool alone (every buffer of a handle belongs to a DevPool member, so deleting the
+    handle frees it and mms_dbg_counter 5 can sum it); the hand-written allocation helpers are gone.  The MMS_LAB-only blocks (the g_blk_counts experiment of
+    ffn_block) are not part of the product library and are left out."""
+    csrc = os.path.join(ROOT, "kddcup_2020_multimodalitiesrecall_2nd_place_amd", "csrc")
+    api = open(os.path.join(csrc, "api.hip")).read()
+    product = re.sub(r"^#ifdef MMS_LAB\b.*?^#(?:else|endif)\b", "", api, flags=re.S | re.M)
+    assert "g_blk_counts" in api and "g_blk_counts" not in product
+    body = re.search(r"struct DevPool \{.*?\n\};", product, flags=re.S).group(0)
+    for call in ("hipMalloc(", "hipFree("):
+        assert product.count(call) == 1, call
+        assert call in body, call
+    for gone in ("free_pool", "dev_alloc", "alloc_planes"):
+        assert gone not in api, gone
