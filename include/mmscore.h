@@ -174,11 +174,11 @@ typedef struct mms_ensemble_batch {
 /* ABI revision of the structs and entry points declared in this header.  It changes whenever a struct gains a field or an entry
  * point changes its signature (r1: 1; r2 added mms_config.fuse_layernorm, mms_zk_batch.label_ids, mms_lxmert_batch.label_ids / x_norm
  * without bumping it; r3: 3, then 4 with mms_config.fuse_attention; r4: 5 -- mms_dbg_gemm takes the engine per call,
- * the process-global mms_set_gemm_variant and the lab engines' hooks left the product library, fuse_layernorm became a mask; r5: 6 -- mms_dbg_qkv_attn and mms_side_lane_flops added; r7: 7 -- mms_decode_feats_b64 added; r8: 8 -- mms_rank_workspace_bytes and mms_rank_submission added; r9: 9 -- mms_ndcg_workspace_bytes, mms_key_relevance and mms_ndcg_at_k added; r10: 10 -- mms_ndcg_sweep_workspace_bytes and mms_ndcg_weight_sweep added; r11: 11 -- mms_filter_sweep_workspace_bytes and mms_filter_sweep added; r12: 12 -- mms_joint_sweep_workspace_bytes and mms_joint_sweep added; r13: 13 -- mms_joint_sweep_codes, mms_resample_workspace_bytes and mms_resample_select added; r14: 14 -- mms_cascade_workspace_bytes, mms_cascade_select and mms_score_ensemble_cascade added).  A caller built against another revision would make the library read past its structs, so compare
+ * the process-global mms_set_gemm_variant and the lab engines' hooks left the product library, fuse_layernorm became a mask; r5: 6 -- mms_dbg_qkv_attn and mms_side_lane_flops added; r7: 7 -- mms_decode_feats_b64 added; r8: 8 -- mms_rank_workspace_bytes and mms_rank_submission added; r9: 9 -- mms_ndcg_workspace_bytes, mms_key_relevance and mms_ndcg_at_k added; r10: 10 -- mms_ndcg_sweep_workspace_bytes and mms_ndcg_weight_sweep added; r11: 11 -- mms_filter_sweep_workspace_bytes and mms_filter_sweep added; r12: 12 -- mms_joint_sweep_workspace_bytes and mms_joint_sweep added; r13: 13 -- mms_joint_sweep_codes, mms_resample_workspace_bytes and mms_resample_select added; r14: 14 -- mms_cascade_workspace_bytes, mms_cascade_select and mms_score_ensemble_cascade added; r15: 15 -- mms_normalize_workspace_bytes and mms_normalize_members added).  A caller built against another revision would make the library read past its structs, so compare
  * BEFORE the first mms_create:  if (mms_version() != MMS_ABI_VERSION) abort();   (lib.py's load() does) */
-#define MMS_ABI_VERSION 14
+#define MMS_ABI_VERSION 15
 int mms_version(void);
-const char* mms_global_error(void);              /* message of the last failing mms_create / mms_decode_feats_b64 / mms_rank_submission / mms_key_relevance / mms_ndcg_at_k / mms_ndcg_weight_sweep / mms_filter_sweep / mms_joint_sweep / mms_joint_sweep_codes / mms_resample_select / mms_cascade_select */
+const char* mms_global_error(void);              /* message of the last failing mms_create / mms_decode_feats_b64 / mms_rank_submission / mms_key_relevance / mms_ndcg_at_k / mms_ndcg_weight_sweep / mms_filter_sweep / mms_joint_sweep / mms_joint_sweep_codes / mms_resample_select / mms_cascade_select / mms_normalize_members */
 
 int mms_create(const mms_config* cfg, mms_handle** out);
 void mms_destroy(mms_handle* h);
@@ -291,6 +291,45 @@ int mms_score_ensemble_cascade(mms_handle* zk, mms_handle* lds, mms_handle* lxme
 int64_t mms_cascade_workspace_bytes(int64_t n);   /* a multiple of 256; -1 for n < 0 or n >= 2^31 */
 int mms_cascade_select(const int64_t* group_ids, const float* score_f32, int64_t n, int32_t keep, uint8_t* kept_u8, int32_t* kept_list_i32,
                        int32_t* status /* [4] */, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Per-query normalisation of the member scores BEFORE a merge (opt-in): every member is put on a common per-query scale, so that the weight and
+ * filter grids of the fits mean the same whatever scale a checkpoint emits.  query_id: device int64 [n]; members: device fp32 [n_members, n],
+ * member-major (the layout mms_score_ensemble writes); out: device fp32 [n_members, n], which must not overlap members.
+ *   A GROUP is all rows with the same query id, in any order, not necessarily adjacent; each member is treated on its own, group by group.  With c
+ *   the rows of the group and x_r = (double)members[m][r] + 0.0 (-0.0 folded onto +0.0), all arithmetic in IEEE double, every operation rounded on
+ *   its own (no fused multiply-add), the result rounded once to fp32:
+ *     MMS_NORMALIZE_MINMAX  (x - lo) / (hi - lo), lo / hi the group's minimum / maximum; +0.0 for every row when hi == lo
+ *     MMS_NORMALIZE_ZSCORE  (x - mean) / sd;  mean = S1 / c, S1 the sum of x_r taken SEQUENTIALLY IN ASCENDING ROW INDEX from +0.0;
+ *                           sd = sqrt(S2 / c), S2 the sum of (x_r - mean) * (x_r - mean) taken the same way; +0.0 for every row unless sd > 0
+ *     MMS_NORMALIZE_RANK    (c - 1 - g) / (c - 1), g the rows of the group whose x is strictly greater (ties share a value); +0.0 when c == 1
+ *     MMS_NORMALIZE_NONE    a copy
+ *   ensemble.normalize_members is the same definition in numpy; the two agree bit for bit.
+ *   status: device int32 [4]:  [0] distinct queries  [1] rows of the largest query  ([0], [1]: over the rows without a flag)  [2] flags  [3] 0
+ *           (MMS_NORMALIZE_NONE checks nothing: a zero status)
+ *   flags:  MMS_NORMALIZE_FLAG_NONFINITE (bit 1)  a non-finite score (NaN, +-inf) in any row of any member
+ *           MMS_NORMALIZE_FLAG_RESERVED_ID (bit 3)  a query id equal to MMS_RANK_RESERVED_ID          (the bits of mms_rank_submission)
+ *   WITH A NON-ZERO FLAG WORD THE CONTENT OF out IS UNSPECIFIED (the transform is skipped): detected, not served -- a caller answers from the host
+ *   form (ensemble.normalize_members_device does).
+ *   workspace: device memory, 256-byte aligned, at least mms_normalize_workspace_bytes(n, n_members) bytes (no content expected, none preserved).
+ * No sort: rows are grouped through a query table and a counting scatter, each list is put into ascending row order by a counting walk, and the
+ * thread of an output element walks its group's list: rows x rows-of-the-query steps per member, no limit on the rows of a query.
+ * Only integer atomics whose result does not depend on arrival order: equal inputs give equal bytes on every run.
+ * The call ONLY ENQUEUES on `stream` (three fills, seven kernels; MMS_NORMALIZE_NONE: one fill, one copy): no allocation, no synchronisation, no
+ * device -> host read.  The caller's current device is restored on return.
+ * Returns MMS_ERR_ARG (message in mms_global_error, nothing launched) for n < 0 or n > MMS_NORMALIZE_MAX_ROWS, n_members outside
+ * [1, MMS_NORMALIZE_MAX_MEMBERS], a mode outside [0, 3], a NULL status, a NULL pointer with n > 0, out overlapping members, a workspace smaller than
+ * mms_normalize_workspace_bytes(n, n_members) or not 256-byte aligned.  n == 0 writes a zero status and returns 0.  Handle-free. */
+#define MMS_NORMALIZE_MAX_ROWS (1 << 22)
+#define MMS_NORMALIZE_MAX_MEMBERS 8
+#define MMS_NORMALIZE_NONE 0
+#define MMS_NORMALIZE_MINMAX 1
+#define MMS_NORMALIZE_ZSCORE 2
+#define MMS_NORMALIZE_RANK 3
+#define MMS_NORMALIZE_FLAG_NONFINITE 2
+#define MMS_NORMALIZE_FLAG_RESERVED_ID 8
+int64_t mms_normalize_workspace_bytes(int64_t n, int32_t n_members);   /* a multiple of 256; -1 for n or n_members out of range */
+int mms_normalize_members(const int64_t* query_id, const float* members, int32_t n_members, int64_t n, int32_t mode, float* out,
+                          int32_t* status /* [4] */, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Box features of B records from their base64 text (the TSV's 6th field: f32 [num_boxes, 2048] row-major), decoded on the device --
  * the host gathers the text (libmmfeat mmf_gather_spans) instead of decoding it, and the H2D copy carries ~42 KB per record instead of 80 KB.

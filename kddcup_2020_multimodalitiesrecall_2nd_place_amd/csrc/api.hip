@@ -2429,6 +2429,29 @@ int mms_cascade_select(const int64_t* group_ids, const float* score_f32, int64_t
     return e.done();
 }
 
+int64_t mms_normalize_workspace_bytes(int64_t n, int32_t n_members) {
+    return n < 0 || n > MMS_NORMALIZE_MAX_ROWS || n_members < 1 || n_members > MMS_NORMALIZE_MAX_MEMBERS ? -1 : (int64_t)normalize_workspace_bytes(n, n_members);
+}
+
+int mms_normalize_members(const int64_t* query_id, const float* members, int32_t n_members, int64_t n, int32_t mode, float* out, int32_t* status,
+                          void* workspace, int64_t workspace_bytes, void* stream) {
+    Entry e{"mms_normalize_members"};
+    e.reject(n < 0 || n > MMS_NORMALIZE_MAX_ROWS, "n must be in [0, MMS_NORMALIZE_MAX_ROWS]");
+    e.reject(n_members < 1 || n_members > MMS_NORMALIZE_MAX_MEMBERS, "n_members must be in [1, MMS_NORMALIZE_MAX_MEMBERS]");
+    e.reject(mode < MMS_NORMALIZE_NONE || mode > MMS_NORMALIZE_RANK, "mode must be one of MMS_NORMALIZE_NONE / MINMAX / ZSCORE / RANK");
+    e.reject(!status, "null status");
+    e.reject(n > 0 && (!query_id || !members || !out), "null pointer");
+    if (!e.bad && n > 0) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(members), b = reinterpret_cast<uintptr_t>(out), bytes = (uintptr_t)n * (uintptr_t)n_members * sizeof(float);
+        e.reject(a < b + bytes && b < a + bytes, "out must not overlap members");
+        e.workspace(workspace, workspace_bytes, (int64_t)normalize_workspace_bytes(n, n_members), "workspace smaller than mms_normalize_workspace_bytes(n, n_members)");
+    }
+    if (e.bad) return e.fail();
+    // (three fills and seven kernels; the launches go to the current device, which the call never changes)
+    launch_normalize_members(query_id, members, n_members, n, mode, out, status, workspace, (hipStream_t)stream);
+    return e.done();
+}
+
 // buffers of the cascade that scale with the call (B pairs) and with the second stage (n_kept pairs): both grow on demand and are kept
 static int ensure_cas_ws(mms_handle* z, int64_t B) {
     DevPool& cas = z->cas_mem;

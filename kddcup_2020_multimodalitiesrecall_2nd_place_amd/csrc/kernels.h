@@ -352,6 +352,12 @@ void launch_cascade_select(const int64_t* group_ids, const float* score, long lo
 void launch_cascade_stage1(const float* probs, long long n, float* x, hipStream_t st);
 void launch_cascade_merge(const float* const probs3[3], const int* kept_list, const int* n_kept_dev, const uint8_t* kept, const float* x, const float w[4],
                           float* merged, float* members, long long n, hipStream_t st);
+// normalize.hip: the member scores on a per-query scale (mms_normalize_members checks the arguments; workspace of normalize_workspace_bytes(n, n_members)
+// bytes, 256-byte aligned).  status = {queries, rows of the largest query, flags, 0}.  Enqueues three fills and seven kernels on st (mode 0: one fill and a
+// copy); allocates nothing, waits for nothing, never changes the current device.
+long long normalize_workspace_bytes(long long n, int n_members);
+void launch_normalize_members(const int64_t* query_id, const float* members, int n_members, long long n, int mode, float* out, int32_t* status,
+                              void* workspace, hipStream_t st);
 // resample.hip: per replicate (a row of counts over the key queries) the first item at the maximum of the count-weighted mean of the byte codes' values
 // (mms_resample_select checks the arguments).  Enqueues four kernels on st; allocates nothing, waits for nothing.
 long long resample_workspace_bytes(long long n_weights, long long n_filters, long long n_key_queries, long long n_replicates);

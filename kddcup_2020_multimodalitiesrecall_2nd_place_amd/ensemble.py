@@ -280,7 +280,133 @@ def _fit(device_call, host_call, use_device, info, soft_flags=0):
     return int(np.argmax(values)), values, rest                                  # the first point that attains the maximum
 
 
-def fit_weights(query_id, product_id, members, rank_label, grid=None, k: int = 5, allow_missing: bool = False, where: str = "device", info: dict = None):
+# ---- per-query normalisation of the member scores in front of a merge (mms_normalize_members, csrc/normalize.hip) ----
+NORMALIZE = ("none", "minmax", "zscore", "rank")          # MMS_NORMALIZE_NONE .. MMS_NORMALIZE_RANK: the index is the library's mode
+NORMALIZE_FLAG_NON_FINITE, NORMALIZE_FLAG_RESERVED_ID = 2, 8                             # status[2] of mms_normalize_members (include/mmscore.h)
+
+
+def _check_normalize(mode):
+    if mode not in NORMALIZE:
+        raise ValueError("normalize must be one of %s, not %r" % (", ".join(repr(m) for m in NORMALIZE), mode))
+
+
+def normalize_members(query_id, members, mode):
+    """The member scores on a common per-query scale, the definition ``mms_normalize_members`` restates: float32 [M, n] from ``members`` float32
+    [M, n] (member-major).  A group is all rows of one query id, in any order, not necessarily adjacent; every member is treated on its own, group
+    by group.  With c rows in the group and x_r = float64(members[m][r]) (-0.0 counts as +0.0), in IEEE double, every operation rounded on its
+    own, the result rounded once to float32:
+      ``"minmax"``  (x - lo) / (hi - lo) with the group's minimum and maximum; +0.0 for every row when hi == lo
+      ``"zscore"``  (x - mean) / sd; mean = S1 / c with S1 the sum of x_r taken sequentially in ascending row index from +0.0, sd = sqrt(S2 / c)
+                    with S2 the sum of (x_r - mean) * (x_r - mean) taken the same way (population variance); +0.0 for every row unless sd > 0
+      ``"rank"``    (c - 1 - g) / (c - 1), g = the rows of the group whose x is strictly greater: the best row 1, the worst 0, ties share a value;
+                    +0.0 when c == 1.  Depends only on the order of the scores inside the group.
+      ``"none"``    ``members`` itself, unchanged.
+    No transcendental function on purpose: the host and the device agree bit for bit."""
+    import numpy as np
+    _check_normalize(mode)
+    if mode == "none":
+        return members
+    q = np.asarray(query_id).astype(np.int64).reshape(-1)
+    mem = np.asarray(members, np.float32)
+    n = len(q)
+    if mem.ndim != 2 or mem.shape[1] != n:
+        raise ValueError("normalize_members: members must be [M, %d], not %s" % (n, tuple(mem.shape)))
+    M = mem.shape[0]
+    out = np.zeros((M, n), np.float32)
+    if n == 0 or M == 0:
+        return out
+    _, inv = np.unique(q, return_inverse=True)
+    order = np.argsort(inv.reshape(-1), kind="stable")                       # grouped by query, ascending row index inside a group
+    gs = inv.reshape(-1)[order]
+    head = np.r_[True, gs[1:] != gs[:-1]]
+    start = np.flatnonzero(head)
+    size = np.diff(np.r_[start, n])
+    grp = np.cumsum(head) - 1                                                # sorted position -> its group
+    c = size.astype(np.float64)
+    x = mem[:, order].astype(np.float64) + 0.0                               # [M, n], grouped; + 0.0 folds -0.0 onto +0.0
+    with np.errstate(all="ignore"):                                          # (a non-finite score: the device flags it and the caller lands here)
+        if mode == "minmax":
+            lo, hi = np.minimum.reduceat(x, start, axis=1)[:, grp], np.maximum.reduceat(x, start, axis=1)[:, grp]
+            res = np.where(hi == lo, 0.0, (x - lo) / (hi - lo))
+        elif mode == "zscore":
+            def seq_sum(term):                                               # per group the sequential sum of term(j-th row of the group), j ascending
+                s = np.zeros((M, len(start)), np.float64)
+                for j in range(int(size.max())):
+                    sel = np.flatnonzero(size > j)
+                    s[:, sel] = s[:, sel] + term(start[sel] + j, sel)
+                return s
+            mean = seq_sum(lambda at, sel: x[:, at]) / c
+
+            def square(at, sel):
+                d = x[:, at] - mean[:, sel]
+                return d * d
+            sd = np.sqrt(seq_sum(square) / c)[:, grp]
+            res = np.where(sd > 0, (x - mean[:, grp]) / sd, 0.0)
+        else:
+            res = np.empty((M, n), np.float64)
+            group_end, cc = (start + size)[grp], c[grp]
+            for m in range(M):
+                o = np.lexsort((x[m], gs))                                   # by group, then score ascending (the groups stay where they are)
+                xs = x[m][o]
+                new = np.r_[True, (xs[1:] != xs[:-1]) | head[1:]]            # first entry of a run of equal scores inside a group
+                run_end = np.r_[np.flatnonzero(new)[1:], n][np.cumsum(new) - 1]
+                greater = (group_end - run_end).astype(np.float64)
+                res[m, o] = np.where(cc > 1, (cc - 1.0 - greater) / np.maximum(cc - 1.0, 1.0), 0.0)
+    out[:, order] = res.astype(np.float32)
+    return out
+
+
+def normalize_members_device(query_id, members, mode, info: dict = None):
+    """``normalize_members`` on the GPU (``mms_normalize_members``): -> device float32 [M, n], bit-equal to the host form.  ``members``: fp32 [M, n]
+    (a device tensor is used in place, and returned as it is for ``"none"``), ``query_id``: int64 [n]; host arrays are copied up once.  Nothing is
+    read back but the status word (one synchronising read).  What the device does not do -- a non-finite score in any member, a query id equal to
+    the reserved -1 -- it detects: the result is then the host form's, uploaded.  ``info`` receives ``{"path": "device" | "host", "flags": int,
+    "queries", "largest_query"}``."""
+    import torch
+
+    from .ndcg import _DeviceCall, _members_on, _on_device, _ptr
+    _check_normalize(mode)
+    dev = next((t.device for t in (members, query_id) if torch.is_tensor(t) and t.is_cuda), torch.device("cuda", torch.cuda.current_device()))
+    mem = _members_on(members, dev)
+    q = _on_device(query_id, dev, torch.int64).reshape(-1)
+    n = q.shape[0]
+    if mem.ndim != 2 or mem.shape[1] != n:
+        raise ValueError("normalize_members_device: members must be [M, %d], not %s" % (n, tuple(mem.shape)))
+    if mode == "none":
+        if info is not None:
+            info.update(path="device", flags=0)
+        return mem
+    call = _DeviceCall(dev)
+    ws_bytes = call.l.mms_normalize_workspace_bytes(n, mem.shape[0])
+    if ws_bytes < 0:
+        raise ValueError("normalize_members_device: %d rows of %d members, the device path takes at most 2^22 rows of 1..8 members" % (n, mem.shape[0]))
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)             # (the caching allocator returns 512-byte aligned blocks)
+    out = torch.empty_like(mem)
+    call("mms_normalize_members", _ptr(q), _ptr(mem), mem.shape[0], n, NORMALIZE.index(mode), _ptr(out), call.status.data_ptr(), ws.data_ptr(), ws_bytes)
+    queries, largest, flags, _ = (int(v) for v in call.status.cpu().numpy())  # the one synchronising read
+    if info is not None:
+        info.update(path="host" if flags else "device", flags=flags, queries=queries, largest_query=largest)
+    if flags:
+        return torch.from_numpy(normalize_members(q.cpu().numpy(), mem.cpu().numpy(), mode)).to(dev)
+    return out
+
+
+def _normalized(query_id, members, normalize, where, info):
+    """The members a ``fit_*`` function sweeps: ``members`` itself for ``"none"``, else normalised ONCE in front of the unchanged sweep -- by the
+    device form for ``where="device"``, by the host form for ``where="host"``; ``info`` then receives ``normalize`` (with ``"none"`` it is today's dict)."""
+    from . import ndcg
+    _check_normalize(normalize)
+    if normalize == "none":
+        return members
+    if info is not None:
+        info["normalize"] = normalize
+    if where == "device":
+        return normalize_members_device(query_id, members, normalize)
+    return normalize_members(ndcg._to_np(query_id), ndcg._member_array(members), normalize)
+
+
+def fit_weights(query_id, product_id, members, rank_label, grid=None, k: int = 5, allow_missing: bool = False, where: str = "device", info: dict = None,
+                normalize: str = "none"):
     """The ensemble weights as a result of the valid set: nDCG@k of the merge ``(...(w0 * s0 + w1 * s1) + ...)`` (``ndcg.merge_members``: IEEE double,
     every operation rounded on its own, main.py:59's evaluation) for every row ``w`` of ``grid`` (default ``weight_grid(M, 20)``), and the winner --
     the FIRST grid row that attains the maximum.  ``members``: fp32 [M, n], member-major (a device tensor stays where it is).
@@ -288,9 +414,13 @@ def fit_weights(query_id, product_id, members, rank_label, grid=None, k: int = 5
     ``where="device"``: ``ndcg.ndcg_sweep_device`` (``mms_ndcg_weight_sweep``: one call for the whole grid); ONE synchronising read carries the
     status and the values.  What the device does not do -- a non-finite merged score of a key query's row, a repeated key query, a reserved id --
     it detects: the values then come from ``ndcg.ndcg_sweep_host``, which ``where="host"`` runs directly; both give the same floats, bit for bit.
-    A key query without rows raises ``KeyError`` unless ``allow_missing``.  ``info`` (a dict) receives ``{"path": "device" | "host", "flags": int}``."""
+    A key query without rows raises ``KeyError`` unless ``allow_missing``.  ``info`` (a dict) receives ``{"path": "device" | "host", "flags": int}``.
+    ``normalize``: one of ``NORMALIZE``; other than ``"none"`` the members are put on a per-query scale ONCE (``normalize_members_device`` for
+    ``where="device"``, ``normalize_members`` for ``"host"``: the same floats) and the sweep runs on the result unchanged; ``info`` then also
+    receives ``normalize``."""
     from . import ndcg
     _check_where(where)
+    members = _normalized(query_id, members, normalize, where, info)
     label_dict = ndcg._label_dict(rank_label)
     grid = _weight_rows(grid, len(members), "fit_weights")
     index, values, _ = _fit(
@@ -333,7 +463,7 @@ def fit_filter(query_id, product_id, score, rank_label, filters=None, k: int = 5
 
 
 def fit_joint(query_id, product_id, members, rank_label, grid=None, filters=None, k: int = 5, allow_missing: bool = False, where: str = "device",
-              info: dict = None):
+              info: dict = None, normalize: str = "none"):
     """The merge weights AND the uniqueness filter as ONE result of the valid set: nDCG@k of the SUBMISSION rows (``ndcg.submission_codes`` on the
     merge ``ndcg.merge_members(members, w)``) for every pair of a row ``w`` of ``grid`` (default ``weight_grid(M, 20)``) and a row ``(gap, tie)`` of
     ``filters`` (default ``filter_grid()``), and the winner -- the FIRST pair that attains the maximum in row-major (weight-major) order.  The filter's
@@ -342,9 +472,13 @@ def fit_joint(query_id, product_id, members, rank_label, grid=None, filters=None
     ``where="device"``: ``ndcg.joint_sweep_device`` (``mms_joint_sweep``: one call for both grids); ONE synchronising read carries the status and the
     values.  What the device does not do -- a (query, product) pair that occurs twice, a non-finite merged score in any row, a repeated key query, a
     reserved id -- it detects: the values then come from ``ndcg.joint_sweep_host``, which ``where="host"`` runs directly; both give the same floats,
-    bit for bit.  A key query without rows raises ``KeyError`` unless ``allow_missing``.  ``info`` receives ``{"path", "flags"}``."""
+    bit for bit.  A key query without rows raises ``KeyError`` unless ``allow_missing``.  ``info`` receives ``{"path", "flags"}``.
+    ``normalize``: one of ``NORMALIZE``; other than ``"none"`` the members are put on a per-query scale ONCE (``normalize_members_device`` for
+    ``where="device"``, ``normalize_members`` for ``"host"``: the same floats) and the sweep runs on the result unchanged; ``info`` then also
+    receives ``normalize``."""
     from . import ndcg
     _check_where(where)
+    members = _normalized(query_id, members, normalize, where, info)
     label_dict = ndcg._label_dict(rank_label)
     grid, filters = _weight_rows(grid, len(members), "fit_joint"), _filter_rows(filters, "fit_joint")
     index, values, _ = _fit(
@@ -389,7 +523,7 @@ def bootstrap_counts(n_key_queries: int, replicates: int = 200, seed: int = 0):
 
 def fit_joint_resampled(query_id, product_id, members, rank_label, grid=None, filters=None, k: int = 5, allow_missing: bool = False,
                         scheme: str = "kfold", folds: int = 5, repeats: int = 4, replicates: int = 200, seed: int = 0, counts=None, probes=(),
-                        where: str = "device", info: dict = None, code_budget: int = RESAMPLE_CODE_BUDGET):
+                        where: str = "device", info: dict = None, code_budget: int = RESAMPLE_CODE_BUDGET, normalize: str = "none"):
     """``fit_joint`` AND how far its winner can be trusted: the maximum of W x G noisy estimates is biased upward, so the fit is repeated on
     resampled answer keys and graded on the key queries each replicate left out -- from the per-query codes of ONE sweep
     (``ndcg.joint_codes_device`` / ``mms_joint_sweep_codes``), because the filter's product statistics are taken over all rows whatever the key.
@@ -405,11 +539,15 @@ def fit_joint_resampled(query_id, product_id, members, rank_label, grid=None, fi
     resampled results.  Any flag ``fit_joint`` falls back on sends this call to the host forms too (``ndcg.joint_sweep_host``,
     ``ndcg.joint_codes_host``, ``ndcg.resample_select_host``), which ``where="host"`` runs directly; ``info`` receives ``{"path", "flags"}``.
     The code matrix takes G * Qa * 64 * ceil(W / 64) bytes (90 MB at the default grids on the valid set); over ``code_budget`` bytes (default
-    4 GiB) the call raises ``ValueError``: fit a coarser grid."""
+    4 GiB) the call raises ``ValueError``: fit a coarser grid.
+    ``normalize``: one of ``NORMALIZE``; other than ``"none"`` the members are put on a per-query scale ONCE (``normalize_members_device`` for
+    ``where="device"``, ``normalize_members`` for ``"host"``: the same floats) and the sweep runs on the result unchanged; ``info`` then also
+    receives ``normalize``."""
     import numpy as np
 
     from . import ndcg
     _check_where(where)
+    members = _normalized(query_id, members, normalize, where, info)
     label_dict = ndcg._label_dict(rank_label)
     Qa = len(label_dict)
     grid, filters = _weight_rows(grid, len(members), "fit_joint_resampled"), _filter_rows(filters, "fit_joint_resampled")

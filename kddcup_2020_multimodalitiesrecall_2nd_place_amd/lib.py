@@ -65,7 +65,7 @@ class RowsSpec(C.Structure):
                ("hm_col0", C.c_int32), ("hm_blocks", C.c_int32)]
 
 
-ABI_VERSION = 14    # include/mmscore.h MMS_ABI_VERSION
+ABI_VERSION = 15    # include/mmscore.h MMS_ABI_VERSION
 
 # enum Engine of csrc/regimes.h (mms_dbg_gemm / mms_dbg_gemm_bench name ONE GEMM engine per call; tests/test_abi.py holds the two lists together)
 ENGINES = {"ENG_AUTO": 0, "ENG_TILE_128": 1, "ENG_TILE_DMA": 3, "ENG_TILE": 4, "ENG_SKINNY": 5, "ENG_TILE_256": 16, "ENG_PP": 20, "ENG_PP_PERSIST": 26,
@@ -79,7 +79,7 @@ EXPORTS = ("mms_version", "mms_global_error", "mms_create", "mms_destroy", "mms_
            "mms_ndcg_workspace_bytes", "mms_key_relevance", "mms_ndcg_at_k", "mms_ndcg_sweep_workspace_bytes", "mms_ndcg_weight_sweep",
            "mms_filter_sweep_workspace_bytes", "mms_filter_sweep", "mms_joint_sweep_workspace_bytes", "mms_joint_sweep",
            "mms_joint_sweep_codes", "mms_resample_workspace_bytes", "mms_resample_select", "mms_cascade_workspace_bytes", "mms_cascade_select",
-           "mms_score_ensemble_cascade")
+           "mms_score_ensemble_cascade", "mms_normalize_workspace_bytes", "mms_normalize_members")
 LAB_EXPORTS = ("mms_dbg_gemm_mx", "mms_lab_ln_trace")      # libmmscore_lab.so only
 
 _lib = None
@@ -118,6 +118,9 @@ def load(path=None):
     lib.mms_cascade_workspace_bytes.argtypes = [i64]
     lib.mms_cascade_workspace_bytes.restype = i64
     lib.mms_cascade_select.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, i64, vp]
+    lib.mms_normalize_workspace_bytes.argtypes = [i64, i32]
+    lib.mms_normalize_workspace_bytes.restype = i64
+    lib.mms_normalize_members.argtypes = [vp, vp, i32, i64, i32, vp, vp, vp, i64, vp]
     lib.mms_decode_feats_b64.argtypes = [vp, vp, vp, i64, vp, vp, vp]
     lib.mms_rank_workspace_bytes.argtypes = [i64]
     lib.mms_rank_workspace_bytes.restype = i64

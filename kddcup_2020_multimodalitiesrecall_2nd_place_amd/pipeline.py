@@ -500,30 +500,67 @@ class EnsembleScorer:
             scores_out.update(query_id=qid, product_id=pid, members=mem)
         return qid, pid, mem, np.cumsum([0] + [int(m.shape[0]) for m, _ in out]).tolist(), rank_label
 
+    @staticmethod
+    def _check_normalize(normalize, cascade_keep=None):
+        from . import ensemble
+        ensemble._check_normalize(normalize)
+        if normalize != "none" and cascade_keep is not None:
+            raise ValueError("normalize=%r with cascade_keep: a pruned pair's zero members have no meaning on a normalised scale" % (normalize,))
+
+    def _normalized_merge(self, qid, mem, normalize, info=None):
+        """The merge the fits grade, on the device: the members [4, n] of a WHOLE file normalised per query (``ensemble.normalize_members_device``: a
+        query cut by a batch boundary is still one group), then ``ndcg.merge_members``'s arithmetic with the scorer's weights in fp64 -- one
+        elementwise kernel per product and per sum, so nothing can be contracted.  -> device fp64 [n]."""
+        from . import ensemble
+        nm = ensemble.normalize_members_device(qid, mem, normalize)
+        if info is not None:
+            info["normalize"] = normalize
+        w = [float(x) for x in self.weights]
+        acc = nm[0].double() * w[0]
+        for m in range(1, nm.shape[0]):
+            prod = nm[m].double() * w[m]
+            acc = acc + prod
+        return acc
+
     def evaluate_tsv_native(self, tsv_path, vocab_path, label_table, rank_label, k: int = 5, metric: str = "device", labels: str = "answer",
                             batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host", info: dict = None, scores_out: dict = None,
-                            cascade_keep: int = None):
+                            cascade_keep: int = None, normalize: str = "none"):
         """A valid TSV file -> nDCG@k of the merged scores against the answer key (``pipeline.evaluate_tsv_native``, which see, for the ensemble):
         the pass of ``score_tsv_native`` with the merged scores left on the device, the zk members' label feed from the answer key
         (``labels="answer"``) or all ones (``labels="ones"``, today's feed), the metric on the GPU (``metric="device"``) or by
         ``ndcg.ndcg_from_arrays`` on the fp64 copy of the scores (``metric="host"``) -- the same float.  ``cascade_keep``: the cascade form of
-        the fused call (``_tsv_pass``); ``info`` also receives ``cascade_kept`` / ``cascade_pairs`` / ``batch_offsets``."""
+        the fused call (``_tsv_pass``); ``info`` also receives ``cascade_kept`` / ``cascade_pairs`` / ``batch_offsets``.
+        ``normalize`` (one of ``ensemble.NORMALIZE``) other than ``"none"``: the pass leaves the four MEMBER scores on the device, they are
+        normalised per query over the whole file and merged in double with the scorer's weights (``_normalized_merge``) -- the merge
+        ``fit_joint_tsv_native(normalize=)`` graded, not the fused call's fp32 merge --, and the metric runs on that score; ``scores_out`` then
+        receives ``members`` too.  Not together with ``cascade_keep`` (``ValueError``)."""
+        self._check_normalize(normalize, cascade_keep)
+        if normalize != "none":
+            _check_eval_args(metric, labels)
+            qid, pid, mem, _, rank_label = self._member_pass(tsv_path, vocab_path, label_table, rank_label, labels, batch_pairs, threads, feat_decode, scores_out)
+            score = self._normalized_merge(qid, mem, normalize, info)
+            if scores_out is not None:
+                scores_out["score"] = score
+            return _metric(qid, pid, score, rank_label, k, metric, False, info)
         qid, pid, score, rank_label = self._merged_pass(tsv_path, vocab_path, label_table, rank_label, labels, batch_pairs, threads, feat_decode, scores_out,
                                                         metric, cascade_keep, info)
         return _metric(qid, pid, score, rank_label, k, metric, False, info)
 
     def fit_weights_tsv_native(self, tsv_path, vocab_path, label_table, rank_label, grid=None, k: int = 5, labels: str = "answer",
-                               batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host", info: dict = None, scores_out: dict = None):
+                               batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host", info: dict = None, scores_out: dict = None,
+                               normalize: str = "none"):
         """A valid TSV file -> the merge weights that maximise nDCG@k against the answer key: ONE pass of ``evaluate_tsv_native`` with the four member
         scores left on the device, then ``ensemble.fit_weights`` over ``grid`` (default ``ensemble.weight_grid(4, 20)``, 1 771 vectors) in one
         library call (``mms_ndcg_weight_sweep``).  -> (weights tuple, value, index, values numpy [W]), the tuple of ``fit_weights``.
         The scorer's own weights are NOT changed: call ``set_weights(best)`` before the testB pass.  ``labels``: the zk members' label feed, as
         in ``evaluate_tsv_native``.  ``scores_out`` (a dict) receives ``query_id`` / ``product_id`` (numpy) and ``members`` (device fp32 [4, n]).
         The value of a weight vector is that of main.py's DOUBLE merge of the fp32 member scores; ``evaluate_tsv_native`` ranks the fp32 merge
-        of the fused call, which can differ on a near tie."""
+        of the fused call, which can differ on a near tie.  ``normalize``: ``ensemble.fit_weights``'s keyword (the members of the whole file are
+        normalised per query in front of the sweep)."""
         from . import ensemble
+        self._check_normalize(normalize)
         qid, pid, mem, _, rank_label = self._member_pass(tsv_path, vocab_path, label_table, rank_label, labels, batch_pairs, threads, feat_decode, scores_out)
-        return ensemble.fit_weights(qid, pid, mem, rank_label, grid, k, info=info)
+        return ensemble.fit_weights(qid, pid, mem, rank_label, grid, k, info=info, normalize=normalize)
 
     def fit_filter_tsv_native(self, tsv_path, vocab_path, label_table, rank_label, filters=None, k: int = 5, labels: str = "answer",
                               batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host", info: dict = None, scores_out: dict = None):
@@ -537,7 +574,8 @@ class EnsembleScorer:
         return ensemble.fit_filter(qid, pid, score, rank_label, filters, k, info=info)
 
     def fit_joint_tsv_native(self, tsv_path, vocab_path, label_table, rank_label, grid=None, filters=None, k: int = 5, labels: str = "answer",
-                             batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host", info: dict = None, scores_out: dict = None):
+                             batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host", info: dict = None, scores_out: dict = None,
+                             normalize: str = "none"):
         """A valid TSV file -> the merge weights AND the uniqueness filter ``(gap, tie)`` that TOGETHER maximise the nDCG@k of the SUBMISSION rows
         against the answer key: ONE pass as ``fit_weights_tsv_native`` (the four member scores left on the device, the zk members' label feed as
         ``labels`` says), then ``ensemble.fit_joint`` over ``grid`` x ``filters`` (defaults ``ensemble.weight_grid(4, 20)`` x
@@ -545,22 +583,26 @@ class EnsembleScorer:
         -> (weights tuple, (gap, tie), value, (iw, ig), values numpy [W, G]), the tuple of ``fit_joint``; pass the winner to ``set_weights`` and to
         ``submission_tsv_native(gap=, tie=)``.  The scorer's own weights are NOT changed.  ``scores_out`` (a dict) receives ``query_id`` /
         ``product_id`` (numpy) and ``members`` (device fp32 [4, n]).  The value is that of main.py's DOUBLE merge of the fp32 member scores; the
-        fused call ranks the fp32 merge, which can differ on a near tie."""
+        fused call ranks the fp32 merge, which can differ on a near tie -- unless both sides normalise: with ``normalize`` other than ``"none"``
+        (``ensemble.fit_joint``'s keyword) the winner goes to ``set_weights`` and ``submission_tsv_native(normalize=, gap=, tie=)``, which ranks
+        exactly the merge graded here."""
         from . import ensemble
+        self._check_normalize(normalize)
         qid, pid, mem, _, rank_label = self._member_pass(tsv_path, vocab_path, label_table, rank_label, labels, batch_pairs, threads, feat_decode, scores_out)
-        return ensemble.fit_joint(qid, pid, mem, rank_label, grid, filters, k, info=info)
+        return ensemble.fit_joint(qid, pid, mem, rank_label, grid, filters, k, info=info, normalize=normalize)
 
     def fit_joint_resampled_tsv_native(self, tsv_path, vocab_path, label_table, rank_label, grid=None, filters=None, k: int = 5, labels: str = "answer",
                                        batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host", info: dict = None, scores_out: dict = None,
-                                       **resample):
+                                       normalize: str = "none", **resample):
         """``fit_joint_tsv_native`` AND the held-out estimate of its winner: ONE pass as there, then ``ensemble.fit_joint_resampled`` on the member
         scores left on the device (``mms_joint_sweep_codes`` + ``mms_resample_select``, one synchronising read).  ``resample``: its keywords
         (``scheme``, ``folds``, ``repeats``, ``replicates``, ``seed``, ``counts``, ``probes``, ``code_budget``).  -> the dict of
         ``fit_joint_resampled``: ``whole`` is the tuple of ``fit_joint_tsv_native``; ``heldout``, ``optimism`` and ``agreement`` say how far to trust
-        it.  The scorer's own weights are NOT changed.  ``scores_out`` as in ``fit_joint_tsv_native``."""
+        it.  The scorer's own weights are NOT changed.  ``scores_out`` and ``normalize`` as in ``fit_joint_tsv_native``."""
         from . import ensemble
+        self._check_normalize(normalize)
         qid, pid, mem, _, rank_label = self._member_pass(tsv_path, vocab_path, label_table, rank_label, labels, batch_pairs, threads, feat_decode, scores_out)
-        return ensemble.fit_joint_resampled(qid, pid, mem, rank_label, grid, filters, k, info=info, **resample)
+        return ensemble.fit_joint_resampled(qid, pid, mem, rank_label, grid, filters, k, info=info, normalize=normalize, **resample)
 
     def cascade_curve_tsv_native(self, tsv_path, vocab_path, label_table, rank_label, keeps, gap: float = None, tie: float = None, k: int = 5,
                                  labels: str = "answer", batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host", where: str = "device",
@@ -596,15 +638,19 @@ class EnsembleScorer:
 
     def submission_tsv_native(self, tsv_path, vocab_path, label_table, out_path=None, batch_pairs: int = 16384, threads: int = 0,
                               feat_decode: str = "host", rank: str = "device", gap: float = None, tie: float = None, cascade_keep: int = None,
-                              info: dict = None):
+                              info: dict = None, normalize: str = "none"):
         """TSV file -> submission rows (``{query: [p1..p5]}``, optionally written to ``out_path``): the pass of ``score_tsv_native`` with the merged
         scores left on the device -- no member scores, no score read-back --, the ids uploaded once, and the uniqueness filter + top-5 on the GPU
         (``ensemble.submission_rows_device``; ``rank="host"``: ``ensemble.submission_rows`` on the fp64 copy of the scores, what a caller of
         ``score_tsv_native`` does).  Same rows either way.  ``gap`` / ``tie``: the filter's constants (``None``: ``ensemble.GAP`` / ``ensemble.TIE``,
         main.py's), e.g. the winner of ``fit_filter_tsv_native``; both rank forms take them.  ``cascade_keep``: the cascade form of the fused call
         (``_tsv_pass``) with the ``keep`` chosen on valid (``cascade_curve_tsv_native``); ``info`` then receives ``cascade_kept`` /
-        ``cascade_pairs`` / ``batch_offsets``."""
+        ``cascade_pairs`` / ``batch_offsets``.  ``normalize`` (one of ``ensemble.NORMALIZE``) other than ``"none"``: the pass's four member scores are
+        normalised per query over the WHOLE file and merged in double with the scorer's weights on the device (``_normalized_merge``), and both rank
+        forms run on that score: with the winner of ``fit_joint_tsv_native(normalize=)`` in ``set_weights`` / ``gap`` / ``tie`` the rows are those
+        the fit graded.  Not together with ``cascade_keep`` (``ValueError``)."""
         from . import ensemble
+        self._check_normalize(normalize, cascade_keep)
         if feat_decode not in ("host", "device"):
             raise ValueError("feat_decode must be 'host' or 'device', not %r" % (feat_decode,))
         if rank not in ("host", "device"):
@@ -612,13 +658,14 @@ class EnsembleScorer:
         gap, tie = ensemble.GAP if gap is None else gap, ensemble.TIE if tie is None else tie
         qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=True, cascade_keep=cascade_keep,
                                        info=info)
-        out = [m for m, _ in out]
         if not out:
             rows = ensemble.submission_rows(qid, pid, np.zeros(0, np.float64), gap, tie)
-        elif rank == "device":
-            rows = ensemble.submission_rows_device(qid, pid, torch.cat(out).double(), gap, tie)
         else:
-            rows = ensemble.submission_rows(qid, pid, torch.cat(out).double().cpu().numpy(), gap, tie)
+            if normalize != "none":
+                score = self._normalized_merge(qid, torch.cat([mem for _, mem in out], 1), normalize, info)
+            else:
+                score = torch.cat([m for m, _ in out]).double()
+            rows = ensemble.submission_rows_device(qid, pid, score, gap, tie) if rank == "device" else ensemble.submission_rows(qid, pid, score.cpu().numpy(), gap, tie)
         if out_path is not None:
             ensemble.write_submission(out_path, rows)
         return rows
