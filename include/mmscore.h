@@ -174,11 +174,11 @@ typedef struct mms_ensemble_batch {
 /* ABI revision of the structs and entry points declared in this header.  It changes whenever a struct gains a field or an entry
  * point changes its signature (r1: 1; r2 added mms_config.fuse_layernorm, mms_zk_batch.label_ids, mms_lxmert_batch.label_ids / x_norm
  * without bumping it; r3: 3, then 4 with mms_config.fuse_attention; r4: 5 -- mms_dbg_gemm takes the engine per call,
- * the process-global mms_set_gemm_variant and the lab engines' hooks left the product library, fuse_layernorm became a mask; r5: 6 -- mms_dbg_qkv_attn and mms_side_lane_flops added; r7: 7 -- mms_decode_feats_b64 added; r8: 8 -- mms_rank_workspace_bytes and mms_rank_submission added; r9: 9 -- mms_ndcg_workspace_bytes, mms_key_relevance and mms_ndcg_at_k added; r10: 10 -- mms_ndcg_sweep_workspace_bytes and mms_ndcg_weight_sweep added; r11: 11 -- mms_filter_sweep_workspace_bytes and mms_filter_sweep added; r12: 12 -- mms_joint_sweep_workspace_bytes and mms_joint_sweep added; r13: 13 -- mms_joint_sweep_codes, mms_resample_workspace_bytes and mms_resample_select added; r14: 14 -- mms_cascade_workspace_bytes, mms_cascade_select and mms_score_ensemble_cascade added; r15: 15 -- mms_normalize_workspace_bytes and mms_normalize_members added).  A caller built against another revision would make the library read past its structs, so compare
+ * the process-global mms_set_gemm_variant and the lab engines' hooks left the product library, fuse_layernorm became a mask; r5: 6 -- mms_dbg_qkv_attn and mms_side_lane_flops added; r7: 7 -- mms_decode_feats_b64 added; r8: 8 -- mms_rank_workspace_bytes and mms_rank_submission added; r9: 9 -- mms_ndcg_workspace_bytes, mms_key_relevance and mms_ndcg_at_k added; r10: 10 -- mms_ndcg_sweep_workspace_bytes and mms_ndcg_weight_sweep added; r11: 11 -- mms_filter_sweep_workspace_bytes and mms_filter_sweep added; r12: 12 -- mms_joint_sweep_workspace_bytes and mms_joint_sweep added; r13: 13 -- mms_joint_sweep_codes, mms_resample_workspace_bytes and mms_resample_select added; r14: 14 -- mms_cascade_workspace_bytes, mms_cascade_select and mms_score_ensemble_cascade added; r15: 15 -- mms_normalize_workspace_bytes and mms_normalize_members added; r16: 16 -- mms_plan_stage, mms_score_ensemble_plan, mms_cascade_safe_workspace_bytes and mms_cascade_select_safe added).  A caller built against another revision would make the library read past its structs, so compare
  * BEFORE the first mms_create:  if (mms_version() != MMS_ABI_VERSION) abort();   (lib.py's load() does) */
-#define MMS_ABI_VERSION 15
+#define MMS_ABI_VERSION 16
 int mms_version(void);
-const char* mms_global_error(void);              /* message of the last failing mms_create / mms_decode_feats_b64 / mms_rank_submission / mms_key_relevance / mms_ndcg_at_k / mms_ndcg_weight_sweep / mms_filter_sweep / mms_joint_sweep / mms_joint_sweep_codes / mms_resample_select / mms_cascade_select / mms_normalize_members */
+const char* mms_global_error(void);              /* message of the last failing mms_create / mms_decode_feats_b64 / mms_rank_submission / mms_key_relevance / mms_ndcg_at_k / mms_ndcg_weight_sweep / mms_filter_sweep / mms_joint_sweep / mms_joint_sweep_codes / mms_resample_select / mms_cascade_select / mms_cascade_select_safe / mms_normalize_members */
 
 int mms_create(const mms_config* cfg, mms_handle** out);
 void mms_destroy(mms_handle* h);
@@ -291,6 +291,58 @@ int mms_score_ensemble_cascade(mms_handle* zk, mms_handle* lds, mms_handle* lxme
 int64_t mms_cascade_workspace_bytes(int64_t n);   /* a multiple of 256; -1 for n < 0 or n >= 2^31 */
 int mms_cascade_select(const int64_t* group_ids, const float* score_f32, int64_t n, int32_t keep, uint8_t* kept_u8, int32_t* kept_list_i32,
                        int32_t* status /* [4] */, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Ensemble PLANS (opt-in): an ordered list of 1 .. MMS_PLAN_MAX_STAGES stages, each naming the members it computes and the rule that decides which
+ * rows go on to the next stage.  mms_score_ensemble is the plan [(7, 0, 0)], mms_score_ensemble_cascade(keep) the plan [(LX, keep, 0), (ZK | LDS, 0, 0)],
+ * and a member subset (e.g. without a member whose weight is zero) is a one-stage plan.
+ *   Members.  MMS_MEMBER_ZK = members 0 and 1 together (one image-token stage), MMS_MEMBER_LDS = member 2, MMS_MEMBER_LX = member 3.
+ *   Stage rules (all rejected with MMS_ERR_ARG before anything is launched): 1 <= n_stages <= MMS_PLAN_MAX_STAGES; every `members` a non-empty subset
+ *     of 7; the stages pairwise disjoint (their union may be a strict subset of 7); reserved == 0; the last stage has keep == safe_k == 0; every other
+ *     stage has exactly one of keep >= 1 / safe_k >= 1; a plan with a safe_k stage and a negative or non-finite weight; a NULL handle (all three are
+ *     required even when a member is in no stage); a NULL group_ids unless the plan has one stage; a NULL reached with B > 0; B >= 2^31.
+ *   Table.  T is fp32 [4][B] and starts as +0.0f.  A_0 = all rows.  Stage s computes its members on the rows A_s and writes them into T.
+ *   Bounds.  L = ((w0 * T0 + w1 * T1) + w2 * T2) + w3 * T3, every product and sum rounded to fp32 on its own (the merge of mms_score_ensemble).  U = the
+ *     same expression with the members of LATER stages set to 1.0f.  Members in no stage stay 0: they are never computed.
+ *   Selection among the rows of A_s, per query (group_ids as for mms_score_ensemble_cascade):
+ *     keep    the order of mms_cascade_select on L (L descending, original row index ascending, -0.0 == +0.0); the first min(keep, rows) go on.
+ *     safe_k  row i is pruned iff at least safe_k OTHER rows j of A_s in its query have L_j > U_i (strict, on the fp32 values): mms_cascade_select_safe.
+ *     A flag at any selection -- a non-finite bound, the reserved id, more than MMS_CASCADE_MAX_ROWS rows -- sends every row of A_s on.
+ *   Output.  member_scores (optional, [4,B]) = T; merged = L of the final T; reached[i] (device uint8 [B]) = the number of stages row i went through
+ *     (1 .. n_stages); n_scored_out[s] (host, optional, [n_stages]) = |A_s|.
+ *   BIT-EQUALITY RULE.  Stage 0 computes its members on b itself.  Stage s > 0 runs on the eleven feed arrays gathered from the ORIGINAL batch through the
+ *     ascending list of A_s; its members are bit-equal to what mms_score_ensemble returns for that gathered batch as a call of its own.  Nothing of an
+ *     earlier stage is reused.  A member of a subset is bit-equal to the same member of mms_score_ensemble on the same batch.
+ *   GUARANTEES, for weights >= 0 and member scores in [0, 1] (fp32 rounding is monotone):
+ *     L <= final merged <= U, whatever values in [0, 1] the members not yet computed take.
+ *     A row pruned by a safe_k stage has at least safe_k rows of its query strictly above it in `merged`: no query's top safe_k of `merged` changes.
+ *     A row kept by a keep stage has merged >= every row of its query pruned at that stage.
+ *     These concern each query's top k of `merged`.  The uniqueness filter of the submission reads every row's score across queries and is NOT covered:
+ *     ensemble.plan_curve measures what a plan changes there.
+ *   Equivalences, bit for bit: [(7, 0, 0)] and mms_score_ensemble (merged, members); [(LX, keep, 0), (ZK | LDS, 0, 0)] and mms_score_ensemble_cascade
+ *     (merged, members, kept = reached == 2, n_kept) -- for w3 > 0, and as long as L = w3 * x separates the lxmert scores x that the cascade's selection
+ *     separates (two scores one ulp apart may round to one L; the tie then goes to the smaller row).
+ *   Cost.  What each stage's mms_score_ensemble costs on its rows, ONE 16-byte device -> host read of the status word per non-last stage, and the copy of
+ *     the feed arrays of the later stages' rows (none while every row has gone on: such a stage runs on b itself, which is the gathered batch).  The buffers live in the zk handle and grow on demand: a warmed-up handle does not allocate.  The
+ *     caller's current device is restored on return. */
+#define MMS_MEMBER_ZK 1
+#define MMS_MEMBER_LDS 2
+#define MMS_MEMBER_LX 4
+#define MMS_PLAN_MAX_STAGES 3
+typedef struct mms_plan_stage { int32_t members; int32_t keep; int32_t safe_k; int32_t reserved; } mms_plan_stage;
+int mms_score_ensemble_plan(mms_handle* zk, mms_handle* lds, mms_handle* lxmert, const mms_ensemble_batch* b, const int64_t* group_ids,
+                            const mms_plan_stage* stages, int32_t n_stages, const float* weights4, float* merged, float* member_scores /* optional [4,B] */,
+                            uint8_t* reached /* [B] */, int64_t* n_scored_out /* host, optional [n_stages] */, void* stream);
+
+/* The safe selection alone, over three parallel device arrays of n rows (group_ids int64, lower_f32, upper_f32): row i is PRUNED iff at least k OTHER
+ * rows j of its group have lower[j] > upper[i] (strict, the fp32 values widened exactly to double, -0.0 == +0.0); every other row is kept.  A group of at
+ * most k rows is kept whole.  kept_u8, kept_list_i32, status, the flags (a non-finite lower OR upper), the workspace rules, "only enqueues" (three fills,
+ * nine kernels), determinism and the argument errors are those of mms_cascade_select, with mms_cascade_safe_workspace_bytes; additionally MMS_ERR_ARG
+ * for k < 1.  lower[i] > upper[i] on a finite row is the caller's error and is not checked.  One wavefront per group, a lane per row, rows x min(rows,
+ * until k are found) comparisons; no limit on the rows of a group or on k.  Handle-free. */
+int64_t mms_cascade_safe_workspace_bytes(int64_t n);   /* a multiple of 256; -1 for n < 0 or n >= 2^31 */
+int mms_cascade_select_safe(const int64_t* group_ids, const float* lower_f32, const float* upper_f32, int64_t n, int32_t k, uint8_t* kept_u8,
+                            int32_t* kept_list_i32, int32_t* status /* [4] as mms_cascade_select */, void* workspace, int64_t workspace_bytes,
+                            void* stream);
 
 /* Per-query normalisation of the member scores BEFORE a merge (opt-in): every member is put on a common per-query scale, so that the weight and
  * filter grids of the fits mean the same whatever scale a checkpoint emits.  query_id: device int64 [n]; members: device fp32 [n_members, n],

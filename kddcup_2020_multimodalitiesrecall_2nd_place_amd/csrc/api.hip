@@ -118,11 +118,12 @@ struct mms_handle {
     DevPool lab_mem, dd_mem;                         // label-text encoder, label-tuple de-duplication
     DevPool lq_mem, lq_store_mem, lq_sub_mem;        // lxmert distinct-query stage: per-pair tables, output store, gather buffers of one sub-batch
     DevPool ens_mem, ens_c_mem, ens_tok_mem, ens_featp_mem;      // fused three-model call: feeds and outputs, changed-query buffers of the second zk member, image tokens, split box features
-    DevPool cas_mem, cas_g_mem;                      // cascade: selection, gathered second-stage batch
+    DevPool cas_mem, cas_g_mem;                      // cascade: selection, gathered second-stage batch (the plan's later stages gather into it too)
+    DevPool plan_mem;                                // plan: member table, stage lists, bounds, selection
     size_t held() const {
         size_t n = 0;
         for (const DevPool* p : {&w_mem, &ws_mem, &kparts_mem, &kparts_side_mem, &lab_mem, &dd_mem, &lq_mem, &lq_store_mem, &lq_sub_mem, &ens_mem, &ens_c_mem,
-                                 &ens_tok_mem, &ens_featp_mem, &cas_mem, &cas_g_mem}) n += p->held;
+                                 &ens_tok_mem, &ens_featp_mem, &cas_mem, &cas_g_mem, &plan_mem}) n += p->held;
         return n;
     }
 
@@ -198,6 +199,10 @@ struct mms_handle {
     float* cas_x = nullptr; int32_t *cas_list = nullptr, *cas_status = nullptr; void* cas_ws = nullptr;
     float *cas_feats = nullptr, *cas_boxes5 = nullptr; int64_t* cas_labels = nullptr;
     int32_t *cas_nb = nullptr, *cas_lab = nullptr, *cas_q = nullptr, *cas_len = nullptr, *cas_q2 = nullptr, *cas_len2 = nullptr, *cas_lxi = nullptr, *cas_lxm = nullptr;
+    // mms_score_ensemble_plan (plan_mem, sized for the call's pairs): member table [4][B], the stage's rows (two lists: current, next), its group ids and bounds
+    // dense by list position, kept bytes / list, one status word per selection, the selection workspace
+    float *plan_T = nullptr, *plan_lo = nullptr, *plan_up = nullptr; int32_t *plan_act[2] = {nullptr, nullptr}, *plan_klist = nullptr, *plan_status = nullptr;
+    int64_t* plan_gid = nullptr; uint8_t* plan_kept = nullptr; void* plan_ws = nullptr;
     Planes ens_featp;      // the wave's split box features when the three members run side by side (they may not live in zk's FFN buffer then)
 
     // ---- gemm timing ----
@@ -2481,6 +2486,28 @@ static int ensure_cas_gather(mms_handle* z, int64_t n, int T, int TL) {
     return g.done(z, n);
 }
 
+// the pairs list[0 .. n) of b as a batch of their own in zk's cas_g_mem (a copy of the eleven feed arrays; the 80 KB of box features per pair in 16-byte accesses)
+static int ens_gather_batch(mms_handle* z, const mms_ensemble_batch* b, const int* list, int64_t n, int T, int TL, hipStream_t st, mms_ensemble_batch* out) {
+    if (int rc = ensure_cas_gather(z, n, T, TL)) return rc;
+    launch_gather_rows_f32x4(b->feats, list, MMS_NBOX * MMS_FEAT, n, z->cas_feats, st);
+    launch_gather_rows_i32((const int32_t*)b->boxes_5, list, MMS_NBOX * 5, n, (int32_t*)z->cas_boxes5, st);     // bit copies of fp32 rows of 50
+    launch_gather_rows_i32(b->num_boxes, list, 1, n, z->cas_nb, st);
+    launch_gather_rows_i32(b->label_ids, list, MMS_NBOX * MMS_LABEL_LEN, n, z->cas_lab, st);
+    launch_gather_rows_i32(b->query_ids, list, T, n, z->cas_q, st);
+    launch_gather_rows_i32(b->len_query, list, 1, n, z->cas_len, st);
+    launch_gather_rows_i32(b->s2f_query_ids, list, T, n, z->cas_q2, st);
+    launch_gather_rows_i32(b->s2f_len_query, list, 1, n, z->cas_len2, st);
+    launch_gather_rows_i64(b->labels, list, 1, n, z->cas_labels, st);
+    launch_gather_rows_i32(b->lx_input_ids, list, TL, n, z->cas_lxi, st);
+    launch_gather_rows_i32(b->lx_input_mask, list, TL, n, z->cas_lxm, st);
+    mms_ensemble_batch g{};
+    g.n_pairs = n; g.feats = z->cas_feats; g.boxes_5 = z->cas_boxes5; g.num_boxes = z->cas_nb; g.label_ids = z->cas_lab; g.query_ids = z->cas_q;
+    g.len_query = z->cas_len; g.s2f_query_ids = z->cas_q2; g.s2f_len_query = z->cas_len2; g.labels = z->cas_labels; g.lx_input_ids = z->cas_lxi;
+    g.lx_input_mask = z->cas_lxm;
+    *out = g;
+    return MMS_OK;
+}
+
 int mms_score_ensemble_cascade(mms_handle* z, mms_handle* l, mms_handle* x, const mms_ensemble_batch* b, const int64_t* group_ids, int32_t keep,
                                const float* weights4, float* merged, float* member_scores, uint8_t* kept, int64_t* n_kept_out, void* stream) {
     if (int rc = ens_check(z, l, x, b, weights4, merged)) return rc;
@@ -2505,27 +2532,130 @@ int mms_score_ensemble_cascade(mms_handle* z, mms_handle* l, mms_handle* x, cons
     const int64_t nk = status[1];
     if (nk < 1 || nk > B) return z->fail(MMS_ERR_STATE, "mms_score_ensemble_cascade: selection returned an impossible count");
     if (n_kept_out) *n_kept_out = nk;
-    // ---- stage 2: the kept pairs, in kept_list order, as a batch of their own (a copy of the eleven feed arrays; the 80 KB of box features per pair in 16-byte accesses) ----
-    if (int rc = ensure_cas_gather(z, nk, T, TL)) return rc;
+    // ---- stage 2: the kept pairs, in kept_list order, as a batch of their own ----
     const int* list = z->cas_list;
-    launch_gather_rows_f32x4(b->feats, list, MMS_NBOX * MMS_FEAT, nk, z->cas_feats, st);
-    launch_gather_rows_i32((const int32_t*)b->boxes_5, list, MMS_NBOX * 5, nk, (int32_t*)z->cas_boxes5, st);     // bit copies of fp32 rows of 50
-    launch_gather_rows_i32(b->num_boxes, list, 1, nk, z->cas_nb, st);
-    launch_gather_rows_i32(b->label_ids, list, MMS_NBOX * MMS_LABEL_LEN, nk, z->cas_lab, st);
-    launch_gather_rows_i32(b->query_ids, list, T, nk, z->cas_q, st);
-    launch_gather_rows_i32(b->len_query, list, 1, nk, z->cas_len, st);
-    launch_gather_rows_i32(b->s2f_query_ids, list, T, nk, z->cas_q2, st);
-    launch_gather_rows_i32(b->s2f_len_query, list, 1, nk, z->cas_len2, st);
-    launch_gather_rows_i64(b->labels, list, 1, nk, z->cas_labels, st);
-    launch_gather_rows_i32(b->lx_input_ids, list, TL, nk, z->cas_lxi, st);
-    launch_gather_rows_i32(b->lx_input_mask, list, TL, nk, z->cas_lxm, st);
     mms_ensemble_batch g{};
-    g.n_pairs = nk; g.feats = z->cas_feats; g.boxes_5 = z->cas_boxes5; g.num_boxes = z->cas_nb; g.label_ids = z->cas_lab; g.query_ids = z->cas_q;
-    g.len_query = z->cas_len; g.s2f_query_ids = z->cas_q2; g.s2f_len_query = z->cas_len2; g.labels = z->cas_labels; g.lx_input_ids = z->cas_lxi;
-    g.lx_input_mask = z->cas_lxm;
+    if (int rc = ens_gather_batch(z, b, list, nk, T, TL, st, &g)) return rc;
     const float* pr2[4];
     if (int rc = ens_run(z, l, x, &g, ENS_ZK | ENS_LDS, st, pr2)) return rc;
     launch_cascade_merge(pr2, list, z->cas_status + 1, kept, z->cas_x, weights4, merged, member_scores, B, st);
+    return post_launch(z);
+}
+
+int64_t mms_cascade_safe_workspace_bytes(int64_t n) {
+    return n < 0 || n > INT32_MAX ? -1 : (int64_t)cascade_safe_workspace_bytes(n);
+}
+
+int mms_cascade_select_safe(const int64_t* group_ids, const float* lower_f32, const float* upper_f32, int64_t n, int32_t k, uint8_t* kept_u8,
+                            int32_t* kept_list_i32, int32_t* status, void* workspace, int64_t workspace_bytes, void* stream) {
+    Entry e{"mms_cascade_select_safe"};
+    e.reject(n < 0 || n > INT32_MAX, "n must be in [0, 2^31)");
+    e.reject(k < 1, "k must be >= 1");
+    e.reject(!status, "null status");
+    e.reject(n > 0 && (!group_ids || !lower_f32 || !upper_f32 || !kept_u8 || !kept_list_i32), "null pointer");
+    if (!e.bad && n > 0)
+        e.workspace(workspace, workspace_bytes, (int64_t)cascade_safe_workspace_bytes(n), "workspace smaller than mms_cascade_safe_workspace_bytes(n)");
+    if (e.bad) return e.fail();
+    // (three fills and nine kernels)
+    launch_cascade_select_safe(group_ids, lower_f32, upper_f32, n, k, kept_u8, kept_list_i32, status, workspace, (hipStream_t)stream);
+    return e.done();
+}
+
+// buffers of a plan that scale with the call (B pairs): grow on demand and are kept
+static int ensure_plan_ws(mms_handle* z, int64_t B) {
+    DevPool& mem = z->plan_mem;
+    if (B <= mem.cap) return MMS_OK;
+    mem.clear();
+    z->plan_T = mem.get<float>(4 * B);
+    z->plan_lo = mem.get<float>(B);
+    z->plan_up = mem.get<float>(B);
+    z->plan_act[0] = mem.get<int32_t>(B);
+    z->plan_act[1] = mem.get<int32_t>(B);
+    z->plan_klist = mem.get<int32_t>(B);
+    z->plan_status = mem.get<int32_t>(4);
+    z->plan_gid = mem.get<int64_t>(B);
+    z->plan_kept = mem.get<uint8_t>(B);
+    z->plan_ws = mem.get<unsigned char>(std::max(cascade_workspace_bytes(B), cascade_safe_workspace_bytes(B)));
+    return mem.done(z, B);
+}
+
+// the stage rules of include/mmscore.h -> nullptr, or what is wrong
+static const char* plan_check(const mms_plan_stage* stages, int32_t n_stages, const float* weights4, const int64_t* group_ids) {
+    if (!stages) return "null stages";
+    if (n_stages < 1 || n_stages > MMS_PLAN_MAX_STAGES) return "n_stages must be in [1, MMS_PLAN_MAX_STAGES]";
+    int seen = 0;
+    bool safe = false;
+    for (int s = 0; s < n_stages; ++s) {
+        const mms_plan_stage& g = stages[s];
+        if (g.members < 1 || g.members > ENS_ALL) return "a stage's members must be a non-empty subset of MMS_MEMBER_ZK | MMS_MEMBER_LDS | MMS_MEMBER_LX";
+        if (g.members & seen) return "a member may be in one stage only";
+        if (g.reserved != 0) return "reserved must be 0";
+        if (g.keep < 0 || g.safe_k < 0) return "keep and safe_k must be >= 0";
+        if (s == n_stages - 1) { if (g.keep != 0 || g.safe_k != 0) return "the last stage selects nothing: keep == safe_k == 0"; }
+        else if ((g.keep >= 1) == (g.safe_k >= 1)) return "every stage but the last needs exactly one of keep >= 1 / safe_k >= 1";
+        seen |= g.members;
+        safe = safe || g.safe_k >= 1;
+    }
+    if (safe && weights4)
+        for (int k = 0; k < 4; ++k)
+            if (!(weights4[k] >= 0.0f) || !std::isfinite(weights4[k])) return "a plan with a safe_k stage needs finite weights >= 0";
+    if (n_stages > 1 && !group_ids) return "null group_ids (only a one-stage plan may leave them out)";
+    return nullptr;
+}
+
+int mms_score_ensemble_plan(mms_handle* z, mms_handle* l, mms_handle* x, const mms_ensemble_batch* b, const int64_t* group_ids, const mms_plan_stage* stages,
+                            int32_t n_stages, const float* weights4, float* merged, float* member_scores, uint8_t* reached, int64_t* n_scored_out,
+                            void* stream) {
+    if (!z || !l || !x) return MMS_ERR_ARG;
+    if (!weights4) return z->fail(MMS_ERR_ARG, "mms_score_ensemble_plan: null weights");
+    if (const char* bad = plan_check(stages, n_stages, weights4, group_ids)) return z->fail(MMS_ERR_ARG, std::string("mms_score_ensemble_plan: ") + bad);
+    if (int rc = ens_check(z, l, x, b, weights4, merged)) return rc;
+    const int64_t B = b->n_pairs;
+    if (B > INT32_MAX) return z->fail(MMS_ERR_ARG, "mms_score_ensemble_plan: too many pairs in one call");
+    if (n_scored_out) for (int s = 0; s < n_stages; ++s) n_scored_out[s] = 0;
+    if (B == 0) return MMS_OK;
+    if (!reached) return z->fail(MMS_ERR_ARG, "mms_score_ensemble_plan: null reached");
+    DeviceScope dev(z->cfg.device);
+    hipStream_t st = (hipStream_t)stream;
+    const int T = z->cfg.text_len, TL = x->cfg.text_len;
+    if (int rc = ensure_plan_ws(z, B)) return rc;
+    HIP_TRY(z, hipMemsetAsync(z->plan_T, 0, (size_t)B * 16, st));             // +0.0f: a member that no stage computes for a row stays there
+    HIP_TRY(z, hipMemsetAsync(reached, 0, (size_t)B, st));
+    const int32_t* act = nullptr;                                             // the stage's rows, ascending; nullptr: every row
+    int64_t n_act = B;
+    int later = 0;
+    for (int s = 0; s < n_stages; ++s) later |= stages[s].members;
+    for (int s = 0; s < n_stages; ++s) {
+        const mms_plan_stage& g = stages[s];
+        later &= ~g.members;
+        // the stage's members on its rows as a batch of their own (stage 0: the caller's batch), scattered into the table
+        mms_ensemble_batch gb{};
+        if (act) { if (int rc = ens_gather_batch(z, b, act, n_act, T, TL, st, &gb)) return rc; }
+        const float* pr[4];
+        if (int rc = ens_run(z, l, x, act ? &gb : b, (unsigned)g.members, st, pr)) return rc;
+        launch_plan_scatter(pr, g.members, act, n_act, z->plan_T, B, reached, st);
+        if (n_scored_out) n_scored_out[s] = n_act;
+        if (s == n_stages - 1) break;
+        // the bounds of these rows, their group ids, the selection among them, and ONE read of its status word
+        launch_plan_bounds(z->plan_T, B, act, n_act, later, weights4, z->plan_lo, g.keep >= 1 ? nullptr : z->plan_up, st);      // (a keep stage reads L only)
+        const int64_t* gid = group_ids;
+        if (act) { launch_gather_rows_i64(group_ids, act, 1, n_act, z->plan_gid, st); gid = z->plan_gid; }
+        if (g.keep >= 1) launch_cascade_select(gid, z->plan_lo, n_act, g.keep, z->plan_kept, z->plan_klist, z->plan_status, z->plan_ws, st);
+        else launch_cascade_select_safe(gid, z->plan_lo, z->plan_up, n_act, g.safe_k, z->plan_kept, z->plan_klist, z->plan_status, z->plan_ws, st);
+        int32_t status[4] = {0, 0, 0, 0};
+        HIP_TRY(z, hipMemcpyAsync(status, z->plan_status, 16, hipMemcpyDeviceToHost, st));
+        HIP_TRY(z, hipStreamSynchronize(st));
+        const int64_t nk = status[1];
+        if (nk < 1 || nk > n_act) return z->fail(MMS_ERR_STATE, "mms_score_ensemble_plan: selection returned an impossible count");
+        if (nk == n_act) continue;      // every row goes on (nothing pruned, or a flag): the list stands -- while it is "all rows" the next stage runs on b itself, no copy
+        // positions in this stage's list -> original rows (still ascending: both lists are)
+        int32_t* next = z->plan_act[act == z->plan_act[0] ? 1 : 0];
+        if (act) launch_gather_rows_i32(act, z->plan_klist, 1, nk, next, st);
+        else HIP_TRY(z, hipMemcpyAsync(next, z->plan_klist, (size_t)nk * 4, hipMemcpyDeviceToDevice, st));
+        act = next;
+        n_act = nk;
+    }
+    launch_plan_merge(z->plan_T, B, weights4, merged, member_scores, st);
     return post_launch(z);
 }
 

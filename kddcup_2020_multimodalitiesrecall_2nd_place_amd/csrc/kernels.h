@@ -352,6 +352,18 @@ void launch_cascade_select(const int64_t* group_ids, const float* score, long lo
 void launch_cascade_stage1(const float* probs, long long n, float* x, hipStream_t st);
 void launch_cascade_merge(const float* const probs3[3], const int* kept_list, const int* n_kept_dev, const uint8_t* kept, const float* x, const float w[4],
                           float* merged, float* members, long long n, hipStream_t st);
+// the safe selection (mms_cascade_select_safe): row i is pruned iff at least k other rows j of its query have lower[j] > upper[i]; the launches, status and
+// flags of launch_cascade_select (a non-finite lower OR upper raises the flag), workspace of cascade_safe_workspace_bytes(n) bytes
+long long cascade_safe_workspace_bytes(long long n);
+void launch_cascade_select_safe(const int64_t* group_ids, const float* lower, const float* upper, long long n, int k, uint8_t* kept, int32_t* kept_list,
+                                int32_t* status, void* workspace, hipStream_t st);
+// around the stages of mms_score_ensemble_plan; T: the [4][n] member table, list: the ascending original rows of a stage's n_stage pairs (nullptr: all rows)
+//   scatter: the stage's [n_stage,2] probabilities of the members in `members` (1 both zk, 2 lds, 4 lxmert) -> T[.][list[t]]; reached[list[t]] += 1
+//   bounds:  lower[t] = the merge of k_merge4 on T[.][list[t]]; upper[t] (optional) = the same with the members of the mask `later` at 1.0f
+//   merge:   merged = the merge of T; members (optional) = T
+void launch_plan_scatter(const float* const probs[4], int members, const int* list, long long n_stage, float* T, long long n, uint8_t* reached, hipStream_t st);
+void launch_plan_bounds(const float* T, long long n, const int* list, long long n_stage, int later, const float w[4], float* lower, float* upper, hipStream_t st);
+void launch_plan_merge(const float* T, long long n, const float w[4], float* merged, float* members, hipStream_t st);
 // normalize.hip: the member scores on a per-query scale (mms_normalize_members checks the arguments; workspace of normalize_workspace_bytes(n, n_members)
 // bytes, 256-byte aligned).  status = {queries, rows of the largest query, flags, 0}.  Enqueues three fills and seven kernels on st (mode 0: one fill and a
 // copy); allocates nothing, waits for nothing, never changes the current device.

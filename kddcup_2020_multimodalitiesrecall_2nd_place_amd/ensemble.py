@@ -709,3 +709,287 @@ def cascade_curve(query_id, product_id, members, rank_label, keeps, weights=WEIG
         changed = sum(1 for qq in set(full_rows) | set(rows) if full_rows.get(qq) != rows.get(qq))
         out.append(dict(keep=int(keep), kept=int(kept.sum()), fraction=float(kept.sum()) / n if n else 1.0, ndcg=float(value), changed=int(changed)))
     return out
+
+
+# ---- plans: ordered stages of members with a rule that decides which rows go on (mms_score_ensemble_plan, include/mmscore.h) ----
+PLAN_MEMBERS = {"zk": 1, "lds": 2, "lxmert": 4}          # MMS_MEMBER_ZK (members 0 and 1 together) / MMS_MEMBER_LDS / MMS_MEMBER_LX
+PLAN_MAX_STAGES = 3
+_PLAN_ROWS = {1: (0, 1), 2: (2,), 4: (3,)}               # member mask bit -> rows of the [4, n] table
+
+
+def _plan_rows(mask):
+    return [r for bit, rows in _PLAN_ROWS.items() if mask & bit for r in rows]
+
+
+def plan(stages):
+    """Normalises a plan to a tuple of ``(members mask, keep, safe_k)`` rows -- the ``mms_plan_stage`` records -- and raises ``ValueError`` on every
+    violation of the stage rules of include/mmscore.h.  A stage is ``(members, rule)``: ``members`` names joined by ``+`` (``"zk"`` = both zk members,
+    ``"lds"``, ``"lxmert"``) or a mask; ``rule`` is ``None`` (the last stage), an int ``keep`` or ``("safe", k)``.  Example:
+    ``[("lxmert", 10), ("zk", ("safe", 5)), ("lds", None)]``.  A normalised plan (rows of three ints) passes through unchanged."""
+    stages = list(stages)
+    if not 1 <= len(stages) <= PLAN_MAX_STAGES:
+        raise ValueError("plan: 1 to %d stages, not %d" % (PLAN_MAX_STAGES, len(stages)))
+    out, seen = [], 0
+    for s, st in enumerate(stages):
+        st = tuple(st) if isinstance(st, (tuple, list)) else (st, None)
+        if len(st) == 3:
+            names, keep, safe_k = st
+            import numbers
+            if any(isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 0 for v in (keep, safe_k)):
+                raise ValueError("plan: stage %d: keep and safe_k must be ints >= 0, not %r / %r" % (s, keep, safe_k))
+            keep, safe_k = int(keep), int(safe_k)
+        elif len(st) == 2:
+            names, rule = st
+            keep = safe_k = 0
+            if rule is None:
+                pass
+            elif isinstance(rule, (tuple, list)):
+                if len(rule) != 2 or rule[0] != "safe" or isinstance(rule[1], bool) or not isinstance(rule[1], (int,)) or rule[1] < 1:
+                    raise ValueError("plan: stage %d: the safe rule is (\"safe\", k) with an int k >= 1, not %r" % (s, rule))
+                safe_k = int(rule[1])
+            elif isinstance(rule, bool) or not isinstance(rule, int) or rule < 1:
+                raise ValueError("plan: stage %d: keep must be an int >= 1, not %r" % (s, rule))
+            else:
+                keep = int(rule)
+        else:
+            raise ValueError("plan: stage %d: (members, rule) expected, not %r" % (s, st))
+        if isinstance(names, str):
+            mask = 0
+            for nm in names.split("+"):
+                nm = nm.strip()
+                if nm not in PLAN_MEMBERS:
+                    raise ValueError("plan: stage %d: unknown member %r (one of %s)" % (s, nm, ", ".join(PLAN_MEMBERS)))
+                if mask & PLAN_MEMBERS[nm]:
+                    raise ValueError("plan: stage %d names %r twice" % (s, nm))
+                mask |= PLAN_MEMBERS[nm]
+        elif isinstance(names, bool) or not isinstance(names, int):
+            raise ValueError("plan: stage %d: members are names joined by + or a mask, not %r" % (s, names))
+        else:
+            mask = names
+        if not 1 <= mask <= 7:
+            raise ValueError("plan: stage %d: the members must be a non-empty subset of zk+lds+lxmert" % s)
+        if mask & seen:
+            raise ValueError("plan: stage %d repeats a member of an earlier stage" % s)
+        seen |= mask
+        if s == len(stages) - 1:
+            if keep or safe_k:
+                raise ValueError("plan: the last stage selects nothing (rule None)")
+        elif (keep >= 1) == (safe_k >= 1):
+            raise ValueError("plan: stage %d needs exactly one of keep >= 1 / (\"safe\", k >= 1)" % s)
+        out.append((mask, keep, safe_k))
+    return tuple(out)
+
+
+def _plan_weights(pl, weights):
+    import numpy as np
+    w = np.asarray(weights, np.float32).reshape(-1)
+    if len(w) != 4:
+        raise ValueError("a plan merges four members, not %d weights" % len(w))
+    if any(sk for _, _, sk in pl) and not (np.isfinite(w).all() and (w >= 0).all()):
+        raise ValueError("a plan with a safe stage needs finite weights >= 0")
+    return w
+
+
+def plan_from_weights(w):
+    """The one-stage plan without the members whose weight is zero (zk: both of its weights): what ``fit_weights`` / ``fit_joint`` may return."""
+    w = [float(x) for x in w]
+    if len(w) != 4:
+        raise ValueError("the ensemble merges four members, not %d" % len(w))
+    mask = (1 if (w[0] != 0.0 or w[1] != 0.0) else 0) | (2 if w[2] != 0.0 else 0) | (4 if w[3] != 0.0 else 0)
+    if not mask:
+        raise ValueError("plan_from_weights: every weight is zero")
+    return plan([(mask, None)])
+
+
+def plan_merge(members, weights):
+    """``((w0 * T0 + w1 * T1) + w2 * T2) + w3 * T3`` in fp32, every product and every sum a numpy operation of its own: ``k_merge4``'s expression."""
+    import numpy as np
+    t = np.asarray(members, np.float32)
+    w = np.asarray(weights, np.float32)
+    p0 = w[0] * t[0]
+    p1 = w[1] * t[1]
+    acc = p0 + p1
+    p2 = w[2] * t[2]
+    acc = acc + p2
+    p3 = w[3] * t[3]
+    acc = acc + p3
+    return acc
+
+
+def cascade_safe_keep(query_id, lower, upper, k: int, parts=None):
+    """The safe selection on the host, the reference of ``mms_cascade_select_safe``: row i is pruned iff at least ``k`` OTHER rows j of its query have
+    ``lower[j] > upper[i]`` (strict; the fp32 values, -0.0 == +0.0).  -> (kept bool [n], kept_list int32).  ``parts`` as ``cascade_keep``."""
+    import numpy as np
+    q = np.asarray(query_id).astype(np.int64).reshape(-1)
+    lo = np.asarray(lower, np.float32).astype(np.float64).reshape(-1) + 0.0
+    up = np.asarray(upper, np.float32).astype(np.float64).reshape(-1) + 0.0
+    n = len(q)
+    if len(lo) != n or len(up) != n:
+        raise ValueError("cascade_safe_keep: %d query ids, %d / %d bounds" % (n, len(lo), len(up)))
+    if k < 1:
+        raise ValueError("cascade_safe_keep: k must be >= 1")
+    kept = np.ones(n, bool)
+    cuts = sorted({0, n} | {int(c) for c in (parts if parts is not None else ()) if 0 < int(c) < n})
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        order = a + np.lexsort((lo[a:b], q[a:b]))                                    # by query, lower ascending
+        qs = q[order]
+        start = np.flatnonzero(np.r_[True, qs[1:] != qs[:-1]])
+        for g0, g1 in zip(start, np.r_[start[1:], b - a]):
+            rows = order[g0:g1]
+            if len(rows) <= k:
+                continue
+            above = len(rows) - np.searchsorted(lo[rows], up[rows], side="right")    # rows of the query with lower > upper[i] ...
+            above = above - (lo[rows] > up[rows])                                   # ... other than i itself
+            kept[rows[above >= k]] = False
+    return kept, np.flatnonzero(kept).astype(np.int32)
+
+
+def cascade_safe_keep_device(query_id, lower, upper, k: int, info: dict = None):
+    """``cascade_safe_keep`` of ONE batch on the GPU (``mms_cascade_select_safe``): -> (kept bool [n], kept_list int32 [n_kept]) as device tensors; one
+    synchronising read of the status word.  On a flag the device keeps every row; the result then comes from the host form.  ``info`` as
+    ``cascade_keep_device``."""
+    import torch
+
+    from .ndcg import _DeviceCall, _ptr, _rows_on_device
+    (lo, up, q), dev = _rows_on_device((lower, upper, query_id), ((torch.float32,), (torch.float32,), (torch.int64,)), "cascade_safe_keep_device")
+    n = lo.shape[0]
+    call = _DeviceCall(dev)
+    ws_bytes = call.l.mms_cascade_safe_workspace_bytes(n)
+    if ws_bytes < 0:
+        raise ValueError("cascade_safe_keep_device: %d rows" % n)
+    ws = torch.empty((max(ws_bytes, 256),), dtype=torch.uint8, device=dev)
+    kept = torch.empty((n,), dtype=torch.uint8, device=dev)
+    kept_list = torch.empty((n,), dtype=torch.int32, device=dev)
+    call("mms_cascade_select_safe", _ptr(q), _ptr(lo), _ptr(up), n, int(k), _ptr(kept), _ptr(kept_list), call.status.data_ptr(), ws.data_ptr(), ws_bytes)
+    flags, n_kept, queries, largest = (int(v) for v in call.status.cpu().numpy())    # the one synchronising read
+    if info is not None:
+        info.update(path="host" if flags else "device", flags=flags, n_kept=n_kept, queries=queries, largest_query=largest)
+    if flags:
+        hk, hl = cascade_safe_keep(q.cpu().numpy(), lo.cpu().numpy(), up.cpu().numpy(), k)
+        return torch.from_numpy(hk).to(dev), torch.from_numpy(hl).to(dev)
+    return kept.bool(), kept_list[:n_kept]
+
+
+def _plan_reached_batch(q, mem, pl, w):
+    """plan_reached of ONE batch (one device call): the table, the bounds and the selections exactly as include/mmscore.h defines them."""
+    import numpy as np
+    n = len(q)
+    table = np.zeros((4, n), np.float32)
+    reached = np.zeros(n, np.uint8)
+    act = np.arange(n)
+    later = 0
+    for mask, _, _ in pl:
+        later |= mask
+    for s, (mask, keep, safe_k) in enumerate(pl):
+        later &= ~mask
+        rows = _plan_rows(mask)
+        table[np.ix_(rows, act)] = mem[np.ix_(rows, act)]
+        reached[act] += 1
+        if s == len(pl) - 1 or len(act) == 0:
+            break
+        lower = plan_merge(table[:, act], w)
+        filled = table[:, act].copy()
+        filled[_plan_rows(later)] = np.float32(1.0)
+        upper = plan_merge(filled, w)
+        flagged = (q[act] == -1).any() or len(act) > (1 << 22) or not np.isfinite(lower).all() or (safe_k >= 1 and not np.isfinite(upper).all())
+        if flagged:
+            continue                                                                 # a flag sends every row of the stage on
+        kept = cascade_keep(q[act], lower, keep)[0] if keep >= 1 else cascade_safe_keep(q[act], lower, upper, safe_k)[0]
+        act = act[kept]
+    return reached
+
+
+def plan_reached(query_id, members, plan_, weights=WEIGHTS, parts=None):
+    """How many stages of ``plan_`` each row goes through (uint8 [n], 1 .. stages), read off a FULL member table (fp32 [4, n], e.g. of
+    ``mms_score_ensemble``): the host definition of ``mms_score_ensemble_plan``'s ``reached``.  All arithmetic in fp32, one operation per statement.
+    ``parts``: batch offsets -- every batch is a call of its own, so a query cut by an offset is selected per part."""
+    import numpy as np
+    pl = plan(plan_)
+    w = _plan_weights(pl, weights)
+    q = np.asarray(query_id).astype(np.int64).reshape(-1)
+    mem = np.asarray(members, np.float32)
+    n = len(q)
+    if mem.shape != (4, n):
+        raise ValueError("plan_reached: members must be [4, %d], not %s" % (n, mem.shape))
+    reached = np.zeros(n, np.uint8)
+    cuts = sorted({0, n} | {int(c) for c in (parts if parts is not None else ()) if 0 < int(c) < n})
+    for a, b in zip(cuts[:-1], cuts[1:]):
+        reached[a:b] = _plan_reached_batch(q[a:b], mem[:, a:b], pl, w)
+    return reached
+
+
+def plan_scored(reached, n_stages: int):
+    """The pairs each stage scores, ``mms_score_ensemble_plan``'s ``n_scored_out``, from ``reached``."""
+    import numpy as np
+    r = np.asarray(reached)
+    return [int((r >= s + 1).sum()) for s in range(n_stages)]
+
+
+def plan_members(members, plan_, reached):
+    """The member table a plan returns for ``reached``: a member's row holds the full table's score where the row reached the member's stage and
+    +0.0 elsewhere (a member of no stage: zeros).  ``members``: fp32 [4, n], numpy or a tensor (the result lives where ``members`` does)."""
+    import numpy as np
+    pl = plan(plan_)
+    if hasattr(members, "detach"):
+        import torch
+        r = torch.as_tensor(np.asarray(reached.cpu() if hasattr(reached, "detach") else reached), device=members.device)
+        out = torch.zeros_like(members)
+        for s, (mask, _, _) in enumerate(pl):
+            for row in _plan_rows(mask):
+                out[row] = torch.where(r >= s + 1, members[row], out[row])
+        return out
+    mem = np.asarray(members, np.float32)
+    r = np.asarray(reached)
+    out = np.zeros_like(mem)
+    for s, (mask, _, _) in enumerate(pl):
+        for row in _plan_rows(mask):
+            out[row] = np.where(r >= s + 1, mem[row], np.float32(0.0))
+    return out
+
+
+def _topk_lists(q, score, k):
+    """{query: the rows of its k best by (score descending, row ascending)}"""
+    import numpy as np
+    order = np.lexsort((np.arange(len(q)), -(score.astype(np.float64) + 0.0), q))
+    qs = q[order]
+    start = np.flatnonzero(np.r_[True, qs[1:] != qs[:-1]]) if len(q) else np.zeros(0, np.int64)
+    return {int(qs[a]): tuple(order[a:min(a + k, b)].tolist()) for a, b in zip(start, np.r_[start[1:], len(q)])}
+
+
+def plan_curve(query_id, product_id, members, rank_label, plans, weights=WEIGHTS, gap=GAP, tie=TIE, k: int = 5, parts=None, where: str = "device"):
+    """What each of ``plans`` costs, read off ONE full pass over the valid set (``members``: fp32 [4, n] of ``mms_score_ensemble``).  -> one dict per plan:
+      ``plan`` (normalised); ``scored``: the pairs each stage scores; ``fraction``: per stage, scored / n;
+      ``ndcg``: nDCG@k of the SUBMISSION rows of the plan's scores -- ``fit_joint`` on ``plan_members`` with the one-row grids ``weights`` and
+      ``(gap, tie)``, so that ``where="device"`` and ``where="host"`` give the same float;
+      ``changed``: the queries whose submission row differs from the full table's (``submission_rows`` on ``ndcg.merge_members``, as ``cascade_curve``);
+      ``topk_changed``: the queries whose top ``k`` of the merged score (fp32, ``plan_merge``; score descending, row ascending) differs from the full
+      table's -- 0 for a plan over all members whose only pruning stages are ``("safe", >= k)``; the uniqueness filter is what ``changed`` shows.
+    What the curve cannot show is the round-off between a later stage's launch regimes and the full pass's (<= 2e-5 on a score, include/mmscore.h)."""
+    import numpy as np
+
+    from . import ndcg
+    _check_where(where)
+    q, p, mem = ndcg._to_np(query_id).astype(np.int64), ndcg._to_np(product_id).astype(np.int64), np.asarray(ndcg._to_np(members), np.float32)
+    n = len(q)
+    grid = np.array([weights], np.float64)
+    filters = np.array([[gap, tie]], np.float64)
+    full_rows = submission_rows(q, p, ndcg.merge_members(mem, grid[0]), gap, tie)
+    full_top = _topk_lists(q, plan_merge(mem, weights), k)
+    out = []
+    for pl in plans:
+        pl = plan(pl)
+        reached = plan_reached(q, mem, pl, weights, parts)
+        pm = plan_members(mem, pl, reached)
+        if where == "device":
+            import torch
+            dev = members.device if hasattr(members, "detach") and members.is_cuda else torch.device("cuda", torch.cuda.current_device())
+            value = fit_joint(query_id, product_id, torch.from_numpy(pm).to(dev), rank_label, grid, filters, k, where="device")[2]
+        else:
+            value = fit_joint(q, p, pm, rank_label, grid, filters, k, where="host")[2]
+        rows = submission_rows(q, p, ndcg.merge_members(pm, grid[0]), gap, tie)
+        changed = sum(1 for qq in set(full_rows) | set(rows) if full_rows.get(qq) != rows.get(qq))
+        top = _topk_lists(q, plan_merge(pm, weights), k)
+        scored = plan_scored(reached, len(pl))
+        out.append(dict(plan=pl, scored=scored, fraction=[float(c) / n if n else 1.0 for c in scored], ndcg=float(value), changed=int(changed),
+                        topk_changed=int(sum(1 for qq in full_top if full_top[qq] != top[qq]))))
+    return out

@@ -58,6 +58,14 @@ class EnsembleBatch(C.Structure):
                 ("lx_input_ids", C.c_void_p), ("lx_input_mask", C.c_void_p)]
 
 
+MEMBER_ZK, MEMBER_LDS, MEMBER_LX, PLAN_MAX_STAGES = 1, 2, 4, 3      # MMS_MEMBER_* / MMS_PLAN_MAX_STAGES
+
+
+class PlanStage(C.Structure):
+    """mms_plan_stage of include/mmscore.h: the members a stage computes (a mask of MEMBER_*) and its rule (exactly one of keep / safe_k; the last stage: neither)."""
+    _fields_ = [(n, C.c_int32) for n in ("members", "keep", "safe_k", "reserved")]
+
+
 class RowsSpec(C.Structure):
     """mms_rows_spec of include/mmscore.h: the addressing fields of one GEMM launch (mms_dbg_gemm_rows; optional on mms_dbg_gemm_f8 / mms_dbg_proj_ln_splitk)."""
     _fields_ = [(n, C.c_int32) for n in ("M", "N", "K", "nsplit", "engine", "act", "reverse", "m_live", "a_rows", "lda")] + [("amap", C.c_int32 * 3), ("r_rows", C.c_int32),
@@ -65,7 +73,7 @@ class RowsSpec(C.Structure):
                ("hm_col0", C.c_int32), ("hm_blocks", C.c_int32)]
 
 
-ABI_VERSION = 15    # include/mmscore.h MMS_ABI_VERSION
+ABI_VERSION = 16    # include/mmscore.h MMS_ABI_VERSION
 
 # enum Engine of csrc/regimes.h (mms_dbg_gemm / mms_dbg_gemm_bench name ONE GEMM engine per call; tests/test_abi.py holds the two lists together)
 ENGINES = {"ENG_AUTO": 0, "ENG_TILE_128": 1, "ENG_TILE_DMA": 3, "ENG_TILE": 4, "ENG_SKINNY": 5, "ENG_TILE_256": 16, "ENG_PP": 20, "ENG_PP_PERSIST": 26,
@@ -79,7 +87,8 @@ EXPORTS = ("mms_version", "mms_global_error", "mms_create", "mms_destroy", "mms_
            "mms_ndcg_workspace_bytes", "mms_key_relevance", "mms_ndcg_at_k", "mms_ndcg_sweep_workspace_bytes", "mms_ndcg_weight_sweep",
            "mms_filter_sweep_workspace_bytes", "mms_filter_sweep", "mms_joint_sweep_workspace_bytes", "mms_joint_sweep",
            "mms_joint_sweep_codes", "mms_resample_workspace_bytes", "mms_resample_select", "mms_cascade_workspace_bytes", "mms_cascade_select",
-           "mms_score_ensemble_cascade", "mms_normalize_workspace_bytes", "mms_normalize_members")
+           "mms_score_ensemble_cascade", "mms_normalize_workspace_bytes", "mms_normalize_members", "mms_score_ensemble_plan",
+           "mms_cascade_safe_workspace_bytes", "mms_cascade_select_safe")
 LAB_EXPORTS = ("mms_dbg_gemm_mx", "mms_lab_ln_trace")      # libmmscore_lab.so only
 
 _lib = None
@@ -118,6 +127,10 @@ def load(path=None):
     lib.mms_cascade_workspace_bytes.argtypes = [i64]
     lib.mms_cascade_workspace_bytes.restype = i64
     lib.mms_cascade_select.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp, i64, vp]
+    lib.mms_score_ensemble_plan.argtypes = [vp, vp, vp, C.POINTER(EnsembleBatch), vp, C.POINTER(PlanStage), i32, C.POINTER(C.c_float), vp, vp, vp, C.POINTER(i64), vp]
+    lib.mms_cascade_safe_workspace_bytes.argtypes = [i64]
+    lib.mms_cascade_safe_workspace_bytes.restype = i64
+    lib.mms_cascade_select_safe.argtypes = [vp, vp, vp, i64, i32, vp, vp, vp, vp, i64, vp]
     lib.mms_normalize_workspace_bytes.argtypes = [i64, i32]
     lib.mms_normalize_workspace_bytes.restype = i64
     lib.mms_normalize_members.argtypes = [vp, vp, i32, i64, i32, vp, vp, vp, i64, vp]

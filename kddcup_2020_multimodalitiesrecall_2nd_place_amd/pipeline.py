@@ -404,8 +404,8 @@ class EnsembleScorer:
         """The merge weights of the following passes (``scorers.EnsembleScorer.set_weights``), e.g. the winner of ``fit_weights_tsv_native``."""
         self.fused.set_weights(w)
 
-    def _score(self, zk_feed, s2f_feed, lx_feed, cascade=None):
-        merged, mem = self.fused(ensemble_feed(zk_feed, s2f_feed, lx_feed), cascade=cascade)[:2]
+    def _score(self, zk_feed, s2f_feed, lx_feed, cascade=None, plan=None):
+        merged, mem = self.fused(ensemble_feed(zk_feed, s2f_feed, lx_feed), cascade=cascade, plan=plan)[:2]
         return merged.double().cpu().numpy(), tuple(m for m in mem.cpu().numpy())
 
     @staticmethod
@@ -413,10 +413,31 @@ class EnsembleScorer:
         if info is not None:
             info.update(cascade_kept=int(kept), cascade_pairs=int(offsets[-1]), batch_offsets=[int(o) for o in offsets])
 
-    def score_lines(self, tsv_lines, label_table, tok_tf, tok_hf, batch_pairs: int = 8192, cascade_keep: int = None, info: dict = None):
+    @staticmethod
+    def _check_plan(plan, cascade_keep=None, normalize="none"):
+        """``plan=`` of the drivers -> the normalised plan (``ensemble.plan``) or None; not together with ``cascade_keep`` or a normalisation."""
+        if plan is None:
+            return None
+        from . import ensemble
+        if cascade_keep is not None:
+            raise ValueError("plan= with cascade_keep: the cascade is the plan [(\"lxmert\", keep), (\"zk+lds\", None)]; give one")
+        if normalize != "none":
+            raise ValueError("plan= with normalize=%r: a member that was not computed is zero, which has no meaning on a normalised scale" % (normalize,))
+        return ensemble.plan(plan)
+
+    @staticmethod
+    def _plan_info(info, scored, offsets):
+        if info is not None:
+            info.update(plan_scored=[int(c) for c in scored], batch_offsets=[int(o) for o in offsets])
+
+    def score_lines(self, tsv_lines, label_table, tok_tf, tok_hf, batch_pairs: int = 8192, cascade_keep: int = None, info: dict = None, plan=None):
         """tok_tf: WordPieceTokenizer as the TF sub-projects build it; tok_hf: the lxmert (HF) flavour.
         ``cascade_keep``: the cascade form of the fused call (``scorers.EnsembleScorer.score_prepared(cascade=)``) with each batch's query ids;
-        ``info`` then receives ``cascade_kept`` / ``cascade_pairs`` (pairs through stage 2 / all pairs) and ``batch_offsets``."""
+        ``info`` then receives ``cascade_kept`` / ``cascade_pairs`` (pairs through stage 2 / all pairs) and ``batch_offsets``.
+        ``plan``: the plan form (``score_prepared(plan=)``; stages as ``ensemble.plan`` takes them) with each batch's query ids; ``info`` then
+        receives ``plan_scored`` (the pairs each stage scored, summed over the batches) and ``batch_offsets``.  Not together with ``cascade_keep``."""
+        plan = self._check_plan(plan, cascade_keep)
+        scored = [0] * len(plan or ())
         lines = [l for l in tsv_lines if l.strip() and "product_id" not in l]
         rec = [F.read_line(l, label_table, tok_tf) for l in lines]
         rec_s2f = [F.read_line(l, label_table, tok_tf, sen2forest=True) for l in lines]
@@ -429,8 +450,11 @@ class EnsembleScorer:
             if not np.array_equal(zf["np_idx_class_labels"], lf["boxes_label_input_ids"]):
                 raise ValueError("the two tokenizer flavours disagree on a class name: the fused entry point takes one label-id tensor")
             cascade = None if cascade_keep is None else (np.array([r.query_id for r in rec[s:s + batch_pairs]], np.int64), cascade_keep)
-            m, p4 = self._score(zf, F.zk_batch(rec_s2f[s:s + batch_pairs], self.zk.cfg.text_len), lf, cascade)
+            pl = None if plan is None else (np.array([r.query_id for r in rec[s:s + batch_pairs]], np.int64), plan)
+            m, p4 = self._score(zf, F.zk_batch(rec_s2f[s:s + batch_pairs], self.zk.cfg.text_len), lf, cascade, pl)
             kept_pairs += self.fused.last_kept if cascade is not None else 0
+            if plan is not None:
+                scored = [a + b for a, b in zip(scored, self.fused.last_scored)]
             merged.append(m)
             for k in range(4):
                 parts[k].append(p4[k])
@@ -439,13 +463,17 @@ class EnsembleScorer:
         pid = np.array([r.product_id for r in rec], np.int64)
         if cascade_keep is not None:
             self._cascade_info(info, kept_pairs, list(range(0, len(rec), batch_pairs)) + [len(rec)])
+        if plan is not None:
+            self._plan_info(info, scored, list(range(0, len(rec), batch_pairs)) + [len(rec)])
         return qid, pid, cat(merged, np.float64), tuple(cat(x, np.float32) for x in parts)
 
-    def _tsv_pass(self, tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members, relabel=None, cascade_keep=None, info=None):
+    def _tsv_pass(self, tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members, relabel=None, cascade_keep=None, info=None,
+                  plan=None):
         """The overlapped pass of the file-fed ensemble drivers with the outputs left on the device: -> (query_id, product_id, per batch: (merged,
         member scores or None without ``members``)).  ``relabel``: see ``_answer_labels``.  ``cascade_keep``: the batch's query ids go to the device
         with the feed and the fused call runs in its cascade form (a query cut by a batch boundary is selected per part); ``info`` receives
-        ``cascade_kept`` / ``cascade_pairs`` and the pass's ``batch_offsets``."""
+        ``cascade_kept`` / ``cascade_pairs`` and the pass's ``batch_offsets``.  ``plan`` (normalised, ``_check_plan``): the same with the plan form;
+        ``info`` receives ``plan_scored`` and ``batch_offsets``."""
         if feat_decode not in ("host", "device"):
             raise ValueError("feat_decode must be 'host' or 'device', not %r" % (feat_decode,))
         # (kept between calls like stream_scores_tsv's; the fused feed reads the 2048-d features from the first pass only, the other two flavours skip their decode)
@@ -457,12 +485,17 @@ class EnsembleScorer:
                     feed = ensemble_feed(zf, nf_s2f.featurize_spans(*span, True), nf_lx.featurize_spans(*span))
                     q, pr = zf["query_id"].copy(), zf["product_id"].copy()
                     ids = {} if relabel is None else {"_query_id": q, "_product_id": pr}
-                    if cascade_keep is not None:
+                    if cascade_keep is not None or plan is not None:
                         ids["_query_id"] = q
                     yield q, pr, {**feed, **{k: zf[k] for k in FEAT_TEXT_KEYS if k in zf}, **ids}
 
             def score(d):
                 prep = self.fused.prepare(d if relabel is None else relabel(d))
+                if plan is not None:
+                    res = self.fused.score_prepared(prep, members, plan=(d["_query_id"], plan))
+                    scored[:] = [a + b for a, b in zip(scored, self.fused.last_scored)]
+                    offsets.append(offsets[-1] + int(res[0].shape[0]))
+                    return res[:2]
                 if cascade_keep is None:
                     return self.fused.score_prepared(prep) if members else self.fused.score_prepared(prep, False)
                 res = self.fused.score_prepared(prep, members, cascade=(d["_query_id"], cascade_keep))
@@ -470,20 +503,22 @@ class EnsembleScorer:
                 offsets.append(offsets[-1] + int(res[0].shape[0]))
                 return res[:2]
 
-            kept, offsets = [0], [0]
+            kept, offsets, scored = [0], [0], [0] * len(plan or ())
             qid, pid, out, _ = _overlapped_pass(batches(), self.zk.device, "feats", score)
             if cascade_keep is not None:
                 self._cascade_info(info, kept[0], offsets)
+            if plan is not None:
+                self._plan_info(info, scored, offsets)
         return qid, pid, out
 
     def _merged_pass(self, tsv_path, vocab_path, label_table, rank_label, labels, batch_pairs, threads, feat_decode, scores_out, metric="device",
-                     cascade_keep=None, info=None):
+                     cascade_keep=None, info=None, plan=None):
         """A pass over a valid file that leaves the MERGED scores on the device, the zk members' label feed as ``labels`` says: -> (query_id,
         product_id, score fp64 [n], the relabelled key); ``scores_out`` receives ``query_id`` / ``product_id`` / ``score``."""
         _check_eval_args(metric, labels)
         rank_label, relabel = _relabel(labels, rank_label, self.zk.device)
         qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=False, relabel=relabel,
-                                       cascade_keep=cascade_keep, info=info)
+                                       cascade_keep=cascade_keep, info=info, plan=plan)
         score = torch.cat([m for m, _ in out]).double() if out else torch.zeros(0, dtype=torch.float64, device=self.zk.device)
         if scores_out is not None:
             scores_out.update(query_id=qid, product_id=pid, score=score)
@@ -524,7 +559,7 @@ class EnsembleScorer:
 
     def evaluate_tsv_native(self, tsv_path, vocab_path, label_table, rank_label, k: int = 5, metric: str = "device", labels: str = "answer",
                             batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host", info: dict = None, scores_out: dict = None,
-                            cascade_keep: int = None, normalize: str = "none"):
+                            cascade_keep: int = None, normalize: str = "none", plan=None):
         """A valid TSV file -> nDCG@k of the merged scores against the answer key (``pipeline.evaluate_tsv_native``, which see, for the ensemble):
         the pass of ``score_tsv_native`` with the merged scores left on the device, the zk members' label feed from the answer key
         (``labels="answer"``) or all ones (``labels="ones"``, today's feed), the metric on the GPU (``metric="device"``) or by
@@ -533,8 +568,10 @@ class EnsembleScorer:
         ``normalize`` (one of ``ensemble.NORMALIZE``) other than ``"none"``: the pass leaves the four MEMBER scores on the device, they are
         normalised per query over the whole file and merged in double with the scorer's weights (``_normalized_merge``) -- the merge
         ``fit_joint_tsv_native(normalize=)`` graded, not the fused call's fp32 merge --, and the metric runs on that score; ``scores_out`` then
-        receives ``members`` too.  Not together with ``cascade_keep`` (``ValueError``)."""
+        receives ``members`` too.  Not together with ``cascade_keep`` (``ValueError``).  ``plan``: the plan form of the fused call (``_tsv_pass``); ``info``
+        also receives ``plan_scored`` / ``batch_offsets``; not together with ``cascade_keep`` or a normalisation (``ValueError``)."""
         self._check_normalize(normalize, cascade_keep)
+        plan = self._check_plan(plan, cascade_keep, normalize)
         if normalize != "none":
             _check_eval_args(metric, labels)
             qid, pid, mem, _, rank_label = self._member_pass(tsv_path, vocab_path, label_table, rank_label, labels, batch_pairs, threads, feat_decode, scores_out)
@@ -543,7 +580,7 @@ class EnsembleScorer:
                 scores_out["score"] = score
             return _metric(qid, pid, score, rank_label, k, metric, False, info)
         qid, pid, score, rank_label = self._merged_pass(tsv_path, vocab_path, label_table, rank_label, labels, batch_pairs, threads, feat_decode, scores_out,
-                                                        metric, cascade_keep, info)
+                                                        metric, cascade_keep, info, plan)
         return _metric(qid, pid, score, rank_label, k, metric, False, info)
 
     def fit_weights_tsv_native(self, tsv_path, vocab_path, label_table, rank_label, grid=None, k: int = 5, labels: str = "answer",
@@ -620,17 +657,34 @@ class EnsembleScorer:
         gap, tie = ensemble.GAP if gap is None else gap, ensemble.TIE if tie is None else tie
         return ensemble.cascade_curve(qid, pid, mem, rank_label, keeps, self.weights, gap, tie, k, parts=offsets, where=where)
 
+    def plan_curve_tsv_native(self, tsv_path, vocab_path, label_table, rank_label, plans, gap: float = None, tie: float = None, k: int = 5,
+                              labels: str = "answer", batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host", where: str = "device",
+                              scores_out: dict = None):
+        """A valid TSV file -> what each plan of ``plans`` would cost: ONE full pass as ``cascade_curve_tsv_native``, then ``ensemble.plan_curve`` with the
+        scorer's merge weights, the filter ``(gap, tie)`` (``None``: main.py's) and the pass's batch offsets as ``parts`` -- per plan the pairs each
+        stage scores, the nDCG@k of the submission rows, the queries whose row changes and those whose top ``k`` of the merged score changes.  Choose
+        a plan here, then pass it as ``plan`` to ``submission_tsv_native`` with the same ``batch_pairs``.  ``scores_out`` as there."""
+        from . import ensemble
+        qid, pid, mem, offsets, rank_label = self._member_pass(tsv_path, vocab_path, label_table, rank_label, labels, batch_pairs, threads, feat_decode,
+                                                               scores_out)
+        if scores_out is not None:
+            scores_out["batch_offsets"] = offsets
+        gap, tie = ensemble.GAP if gap is None else gap, ensemble.TIE if tie is None else tie
+        return ensemble.plan_curve(qid, pid, mem, rank_label, plans, self.weights, gap, tie, k, parts=offsets, where=where)
+
     def score_tsv_native(self, tsv_path, vocab_path, label_table, batch_pairs: int = 16384, threads: int = 0, feat_decode: str = "host",
-                         cascade_keep: int = None, info: dict = None):
+                         cascade_keep: int = None, info: dict = None, plan=None):
         """``score_lines`` on a TSV file through libmmfeat, decode and scoring overlapped: a producer thread decodes span batch i+1
         three times (zk flavour, zk with the sen2forest rewrite, lxmert flavour; ctypes releases the GIL, each featurizer rotates
         three pinned buffer sets) while the main thread copies batch i to the device and runs the ONE fused call on it.
         ``feat_decode="device"``: the zk-flavour pass gathers the features' base64 text and the GPU decodes it on the scoring stream in front of
         the fused call (``stream_scores_tsv``); same scores, a bad record raises ValueError before the pass returns.
         ``cascade_keep``: the cascade form of the fused call (``_tsv_pass``; members 0-2 of a pruned pair are zeros); ``info`` then receives
-        ``cascade_kept`` / ``cascade_pairs`` / ``batch_offsets``."""
+        ``cascade_kept`` / ``cascade_pairs`` / ``batch_offsets``.  ``plan``: the plan form (``_tsv_pass``; a member that was not computed for a pair is
+        zero); ``info`` then receives ``plan_scored`` / ``batch_offsets``."""
+        plan = self._check_plan(plan, cascade_keep)
         qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=True, cascade_keep=cascade_keep,
-                                       info=info)
+                                       info=info, plan=plan)
         if not out:
             return qid, pid, np.zeros(0, np.float64), tuple(np.zeros(0, np.float32) for _ in range(4))
         mem_all = torch.cat([mem for _, mem in out], 1).cpu().numpy()
@@ -638,7 +692,7 @@ class EnsembleScorer:
 
     def submission_tsv_native(self, tsv_path, vocab_path, label_table, out_path=None, batch_pairs: int = 16384, threads: int = 0,
                               feat_decode: str = "host", rank: str = "device", gap: float = None, tie: float = None, cascade_keep: int = None,
-                              info: dict = None, normalize: str = "none"):
+                              info: dict = None, normalize: str = "none", plan=None):
         """TSV file -> submission rows (``{query: [p1..p5]}``, optionally written to ``out_path``): the pass of ``score_tsv_native`` with the merged
         scores left on the device -- no member scores, no score read-back --, the ids uploaded once, and the uniqueness filter + top-5 on the GPU
         (``ensemble.submission_rows_device``; ``rank="host"``: ``ensemble.submission_rows`` on the fp64 copy of the scores, what a caller of
@@ -648,16 +702,19 @@ class EnsembleScorer:
         ``cascade_pairs`` / ``batch_offsets``.  ``normalize`` (one of ``ensemble.NORMALIZE``) other than ``"none"``: the pass's four member scores are
         normalised per query over the WHOLE file and merged in double with the scorer's weights on the device (``_normalized_merge``), and both rank
         forms run on that score: with the winner of ``fit_joint_tsv_native(normalize=)`` in ``set_weights`` / ``gap`` / ``tie`` the rows are those
-        the fit graded.  Not together with ``cascade_keep`` (``ValueError``)."""
+        the fit graded.  Not together with ``cascade_keep`` (``ValueError``).  ``plan``: the plan form of the fused call (``_tsv_pass``) with the plan chosen
+        on valid (``plan_curve_tsv_native``); ``info`` then receives ``plan_scored`` / ``batch_offsets``; not together with ``cascade_keep`` or a
+        normalisation (``ValueError``)."""
         from . import ensemble
         self._check_normalize(normalize, cascade_keep)
+        plan = self._check_plan(plan, cascade_keep, normalize)
         if feat_decode not in ("host", "device"):
             raise ValueError("feat_decode must be 'host' or 'device', not %r" % (feat_decode,))
         if rank not in ("host", "device"):
             raise ValueError("rank must be 'host' or 'device', not %r" % (rank,))
         gap, tie = ensemble.GAP if gap is None else gap, ensemble.TIE if tie is None else tie
         qid, pid, out = self._tsv_pass(tsv_path, vocab_path, label_table, batch_pairs, threads, feat_decode, members=True, cascade_keep=cascade_keep,
-                                       info=info)
+                                       info=info, plan=plan)
         if not out:
             rows = ensemble.submission_rows(qid, pid, np.zeros(0, np.float64), gap, tie)
         else:

@@ -369,14 +369,44 @@ class EnsembleScorer:
                                t["labels"].data_ptr(), t["lx"].data_ptr(), t["lxm"].data_ptr())
         return s, B, t
 
-    def score_prepared(self, prepared, members: bool = True, cascade=None):
+    def score_prepared(self, prepared, members: bool = True, cascade=None, plan=None):
         """-> (merged [B], member scores [4,B] or None), device fp32.
+        ``plan=(group_ids, stages)``: the plan form (``mms_score_ensemble_plan``, include/mmscore.h) -- ``stages`` as ``ensemble.plan`` takes them,
+        ``group_ids`` [B] the query id of each pair (``None`` for a one-stage plan) -- -> (merged, members, reached [B] uint8: the stages each pair
+        went through); ``self.last_scored`` = the pairs each stage scored.  A member that was not computed for a pair is exactly +0.0.
         ``cascade=(group_ids, keep)``: the cascade form (``mms_score_ensemble_cascade``, include/mmscore.h) -- lxmert scores every pair, the best
         ``keep`` pairs of each query (``group_ids`` [B]: the query id of each pair) go through the other three members, a pruned pair's members
         0-2 are exact zeros -- -> (merged, members, kept [B] bool); ``self.last_kept`` = the number of kept pairs."""
+        if plan is not None and cascade is not None:
+            raise ValueError("plan= and cascade= are two forms of one call: give one")
         s, B, keep = prepared
         merged = torch.empty((B,), device=self.device, dtype=torch.float32)
         mem = torch.empty((4, B), device=self.device, dtype=torch.float32) if members else None
+        if plan is not None:
+            from . import ensemble as _ens
+            group_ids, stages = plan
+            stages = _ens.plan(stages)
+            _ens._plan_weights(stages, self.weights)
+            if group_ids is None and len(stages) > 1:
+                raise ValueError("plan: only a one-stage plan may leave the group ids out")
+            gid = None
+            if group_ids is not None:
+                gid = self.zk._dev(group_ids, torch.int64)
+                if gid.shape != (B,):
+                    raise ValueError("plan: group_ids must hold one query id per pair")
+            rec = (_lib.PlanStage * len(stages))(*[_lib.PlanStage(m, k, sk, 0) for m, k, sk in stages])
+            reached = torch.zeros((B,), device=self.device, dtype=torch.uint8)
+            scored = (_lib.C.c_int64 * len(stages))()
+            if B > 0:
+                st = torch.cuda.current_stream(self.device).cuda_stream
+                rc = self.lib.mms_score_ensemble_plan(self.zk.handle._h, self.lds.handle._h, self.lxmert.handle._h, _lib.C.byref(s),
+                                                      gid.data_ptr() if gid is not None else None, rec, len(stages), self.w, merged.data_ptr(),
+                                                      mem.data_ptr() if members else None, reached.data_ptr(), scored, st)
+                if rc != 0:
+                    raise _lib.MmsError("mms_score_ensemble_plan failed (%d): %s" % (rc, self.lib.mms_last_error(self.zk.handle._h).decode()))
+            self._keep = (keep, gid)
+            self.last_scored = [int(v) for v in scored]
+            return merged, mem, reached
         if cascade is not None:
             group_ids, n_keep = cascade
             gid = self.zk._dev(group_ids, torch.int64)
@@ -403,8 +433,10 @@ class EnsembleScorer:
         self._keep = keep
         return merged, mem
 
-    def __call__(self, feed: dict, members: bool = True, cascade=None):
-        return self.score_prepared(self.prepare(feed), members, cascade)
+    def __call__(self, feed: dict, members: bool = True, cascade=None, plan=None):
+        if plan is not None and cascade is not None:
+            raise ValueError("plan= and cascade= are two forms of one call: give one")
+        return self.score_prepared(self.prepare(feed), members, cascade, plan)
 
     def close(self):
         for m in (self.zk, self.lds, self.lxmert):
